@@ -118,6 +118,15 @@ int rng_ntt_fr_dev_oop(RngCtx* ctx, void* dev_in, void* dev_out, uint64_t n,
 int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,
                    uint64_t n, uint64_t* out9, int window_c);
 
+/* Batched MSM against the context's SRS, through the same call the prover's
+ * commitments use: B polynomials of n CANONICAL scalars each (host, B*n*4
+ * u64) against the first n SRS points.  window_c in [8,16], 0 = auto.
+ * mode 0 = auto (fixed-base window table where one is allowed, else
+ * windowed), 1 = fixed-base (error if no table can be built), 2 = windowed
+ * variable-base Pippenger.  out = B affine records of 9 u64. */
+int rng_msm_srs_batch(RngCtx* ctx, const uint64_t* scalars, uint64_t n, uint32_t B,
+                      int window_c, int mode, uint64_t* out9xB);
+
 /* Device buffer helpers */
 void* rng_dbuf_alloc(size_t bytes);
 void rng_dbuf_free(void* dbuf);

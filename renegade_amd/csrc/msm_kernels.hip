@@ -24,6 +24,17 @@
 //     the HOST (a 1-lane dependent EC chain is far faster on a host core).
 // A GLV-endomorphism variant and a fused suffix-scan fold exist behind
 // RNG_MSM_GLV / RNG_MSM_FOLD (both measured slower on MI355X).
+//
+// Fixed-base mode (every commitment against the context's SRS):
+// the bases never change, so k_msm_fixed_table precomputes
+// T[w*N + i] = 2^(c*w) * P_i once per window size c.  k_msm_digits_fixed
+// then writes key = poly<<c | magnitude and val = sign<<31 | (w*N + i): all
+// W digits of a polynomial share ONE bucket set (key group = poly), the
+// sort covers c + ceil(log2(B+1)) bits, bucket_reduce gathers from the
+// table, stages 4-5 see B groups instead of B*W, and the host Horner fold
+// disappears.  c comes from msm_fixed_c (cost-based; no top-window rule).
+// The variable-base pipeline above is unchanged and still serves
+// caller-supplied bases (rng_msm_g1*), RNG_MSM_FIXED=0, GLV and BINNED.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -99,6 +110,110 @@ __global__ __launch_bounds__(256) void k_msm_digits(const uint64_t* scalars, uin
         vals[o] = (sign << 31) | i;
     }
     // carry out of the top window must be zero for scalars < 2^(W*c-1)
+}
+
+// ---- 1-fixed. fixed-base mode (SRS commitments) ----
+// The SRS never changes for the life of a context, so the window weights
+// 2^(c*w) are folded into a precomputed table T[w*N + i] = 2^(c*w) * P_i.
+// Every digit of a scalar then indexes its own table point and ALL W digits
+// of a polynomial fall into ONE bucket set: key group = poly, W times fewer
+// buckets, no per-window aggregation and no host Horner fold.
+
+// window size on the fixed-base path, by per-poly point count n and batch B.
+// There is no separate top window here (all windows share one bucket set),
+// so the {8,13,16} "populated top window" rule of msm_auto_c does not apply
+// and c is chosen by cost: n*W(c) mixed adds + ~2*2^(c-1) aggregation adds
+// per poly.  What still matters is the bucket COUNT B*2^(c-1): a bucket
+// holds n*W/2^(c-1) entries, and its sub-segment partials are merged by one
+// lane, so few big buckets mean a long serial chain.  Measured on MI355X
+// (DESIGN §4.1): c=10 wins the fused cohort rounds at the settlement size;
+// small batches (single proofs, preprocessing, link proofs) and the large
+// domains keep c=13, whose bucket count equals the windowed path's at c=8.
+// At most three values, so at most three tables per context.
+__host__ __device__ inline uint32_t msm_fixed_c(uint64_t n, uint32_t B) {
+    if (n <= (1ull << 8)) return 8;
+    if (B >= 16 && n < (1ull << 13)) return 10;
+    return 13;
+}
+
+constexpr uint32_t MSM_FIXED_MAX_W = 32;  // W(c) = ceil(256/c) <= 32 for c >= 8
+
+// table build: one thread per base walks its W windows (c Jacobian
+// doublings each), parks (X, Y) in the table slot, then normalises all W
+// points with ONE field inversion (Montgomery batch inversion over the
+// thread's own Z values).  Bases have prime order, so no multiple is the
+// identity and every Z is invertible.
+__global__ __launch_bounds__(256) void k_msm_fixed_table(const G1Aff* bases, uint32_t N,
+                                                         uint32_t c, uint32_t W,
+                                                         G1Aff* table) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    Fq zs[MSM_FIXED_MAX_W], pref[MSM_FIXED_MAX_W];  // pref[j] = Z_0 * ... * Z_j
+    G1Jac acc = G1Jac::from_affine(bases[i]);
+    Fq run = Fq::one();
+    for (uint32_t j = 0; j < W; ++j) {
+        if (j)
+            for (uint32_t k = 0; k < c; ++k) acc = acc.dbl();
+        G1Aff parked;
+        parked.x = acc.X;
+        parked.y = acc.Y;
+        table[(uint64_t)j * N + i] = parked;
+        zs[j] = acc.Z;
+        run = run.mul(acc.Z);
+        pref[j] = run;
+    }
+    Fq inv = run.inverse();  // 1 / (Z_0 * ... * Z_{W-1})
+    for (int j = (int)W - 1; j >= 0; --j) {
+        Fq zinv = j ? inv.mul(pref[j - 1]) : inv;
+        inv = inv.mul(zs[j]);
+        Fq zinv2 = zinv.sqr();
+        G1Aff p = table[(uint64_t)j * N + i];
+        p.x = p.x.mul(zinv2);
+        p.y = p.y.mul(zinv2.mul(zinv));
+        table[(uint64_t)j * N + i] = p;
+    }
+}
+
+// digits for the fixed-base mode: key = poly << c | magnitude (the magnitude
+// reaches 2^(c-1) inclusive, so it needs c bits), val = sign << 31 | table
+// index w*N + i.  Zero digits get the sentinel B << c.
+__global__ __launch_bounds__(256) void k_msm_digits_fixed(const uint64_t* scalars,
+                                                          uint32_t n, uint32_t c,
+                                                          uint32_t W, uint32_t B,
+                                                          uint32_t N, uint32_t* keys,
+                                                          uint32_t* vals) {
+    uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * B) return;
+    uint32_t b = idx / n, i = idx % n;
+    uint64_t s[4];
+    s[0] = scalars[4 * idx];
+    s[1] = scalars[4 * idx + 1];
+    s[2] = scalars[4 * idx + 2];
+    s[3] = scalars[4 * idx + 3];
+    uint32_t carry = 0;
+    uint32_t half = 1u << (c - 1);
+    uint64_t cmask = (1ull << c) - 1;
+    for (uint32_t w = 0; w < W; ++w) {
+        uint32_t bit0 = w * c;
+        uint32_t limb = bit0 >> 6, off = bit0 & 63;
+        uint64_t raw = limb < 4 ? s[limb] >> off : 0;
+        if (off + c > 64 && limb + 1 < 4) raw |= s[limb + 1] << (64 - off);
+        raw = (raw & cmask) + carry;
+        uint32_t mag, sign;
+        if (raw > half) {  // negative digit raw - 2^c, carry into the next window
+            mag = (uint32_t)((1ull << c) - raw);
+            sign = 1;
+            carry = 1;
+        } else {  // raw == half stays +half, no carry
+            mag = (uint32_t)raw;
+            sign = 0;
+            carry = 0;
+        }
+        uint64_t o = ((uint64_t)b * W + w) * n + i;
+        keys[o] = mag == 0 ? (B << c) : ((b << c) | mag);
+        vals[o] = (sign << 31) | (w * N + i);
+    }
+    // carry out of the top window is zero: scalars < 2^254 <= 2^(W*c-1)
 }
 
 // ---- 1-alt. binned (counting-scatter) pipeline ----
@@ -429,6 +544,18 @@ __host__ inline uint32_t msm_seg_cap(uint64_t total_entries) {
     return (uint32_t)cap;
 }
 
+// fixed-base mode: a bucket holds n*W/2^(c-1) entries (W times the windowed
+// path's), so the cap trades bucket-reduce lanes against Jacobian adds in
+// k_msm_seg_merge; RNG_MSM_SEGCAP (8..128) overrides for tuning sweeps
+__host__ inline uint32_t msm_fixed_seg_cap(uint64_t total_entries) {
+    static int cap_env = [] {
+        const char* e = getenv("RNG_MSM_SEGCAP");
+        return e ? atoi(e) : 0;
+    }();
+    if (cap_env >= 8 && cap_env <= (int)MSM_MAX_SEG) return (uint32_t)cap_env;
+    return msm_seg_cap(total_entries);
+}
+
 // ---- 3b. segment lengths + sub-segment counts ----
 // heads are in increasing order (rocprim::select is stable); seg i spans
 // [heads[i], heads[i+1] or first sentinel/total).
@@ -502,7 +629,7 @@ __global__ __launch_bounds__(256) void k_msm_seg_merge(
     const uint32_t* keys, const uint32_t* heads, const uint32_t* sub_off,
     const uint32_t* nsub, const uint32_t* head_order /* by nsub desc */,
     uint32_t head_count, const G1Jac* partials2,
-    G1Jac* buckets, uint32_t c) {
+    G1Jac* buckets, uint32_t c, uint32_t key_shift /* 16, or c in fixed-base mode */) {
     uint32_t tt = blockIdx.x * blockDim.x + threadIdx.x;
     if (tt >= head_count) return;
     uint32_t t = head_order[tt];
@@ -510,8 +637,8 @@ __global__ __launch_bounds__(256) void k_msm_seg_merge(
     G1Jac acc = partials2[off];
     for (uint32_t k = 1; k < ns; ++k) acc = acc.add(partials2[off + k]);
     uint32_t key = keys[heads[t]];
-    uint32_t w = key >> 16;
-    uint32_t mag = key & 0xFFFFu;  // 1 .. 2^(c-1)
+    uint32_t w = key >> key_shift;
+    uint32_t mag = key & ((1u << key_shift) - 1);  // 1 .. 2^(c-1)
     buckets[(uint64_t)w * (1u << (c - 1)) + (mag - 1)] = acc;
 }
 

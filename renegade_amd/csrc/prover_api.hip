@@ -231,6 +231,13 @@ struct RngCtxImpl {
     uint64_t srs_count = 0;
     void* srs_dev = nullptr;
     void* srs_glv_dev = nullptr;  // [P, phi(P)] interleaved for GLV
+    // fixed-base window tables T[j*srs_count + i] = 2^(c*j) * P_i, built
+    // lazily per window size c (msm_fixed_c returns at most three values)
+    struct FixedTable {
+        uint32_t c = 0;
+        void* dev = nullptr;
+    };
+    FixedTable fixed_tables[3];
     uint64_t h_g2[16];       // h: x.c0,x.c1,y.c0,y.c1 Montgomery
     uint64_t beta_h_g2[16];
     std::map<uint32_t, std::unique_ptr<NttPlan>> plans;
@@ -246,6 +253,7 @@ struct RngCtxImpl {
         }
         hip_free_guarded(srs_dev);
         hip_free_guarded(srs_glv_dev);
+        for (auto& t : fixed_tables) hip_free_guarded(t.dev);
     }
 };
 
@@ -442,15 +450,36 @@ static inline bool msm_glv_enabled() {
     return v != 0;
 }
 
+static inline bool msm_binned_enabled() {
+    static int v = [] {
+        const char* e = getenv("RNG_MSM_BINNED");
+        return e ? atoi(e) : 0;
+    }();
+    return v != 0;
+}
+
 static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t n,
                        uint32_t c, G1Jac* h_result, uint32_t B = 1,
                        hipStream_t stream = RNG_STREAM,
-                       const G1Aff* d_glv_bases = nullptr) {
-    const bool glv = msm_glv_enabled();
+                       const G1Aff* d_glv_bases = nullptr,
+                       const G1Aff* d_fixed_table = nullptr,
+                       uint64_t fixed_stride = 0) {
+    // fixed-base mode (d_fixed_table = window table for this c, fixed_stride =
+    // its row length N): every digit gathers its own pre-weighted table point,
+    // so a poly's W digit positions share ONE bucket set (key group = poly)
+    // and the fold below sees a single "window".  Callers pass a table only
+    // when neither RNG_MSM_GLV nor RNG_MSM_BINNED is set (msm_srs_run).
+    const bool fixed = d_fixed_table != nullptr;
+    const bool glv = !fixed && msm_glv_enabled();
     // GLV halves scalar width: two 127-bit halves share each window's buckets
     uint32_t W = glv ? (128 + c - 1) / c : (256 + c - 1) / c;
+    const uint32_t Wd = W;  // digit positions per scalar
+    if (fixed) W = 1;       // windows per poly as seen by buckets/aggregation/fold
     uint32_t G = B * W;  // key groups
-    uint64_t per_scalar_entries = glv ? 2 * W : W;
+    // keys pack group << key_shift | magnitude; the fixed mode packs tightly
+    // (magnitude <= 2^(c-1) needs c bits) so the sort touches c + gb bits
+    const uint32_t key_shift = fixed ? c : 16;
+    uint64_t per_scalar_entries = glv ? 2 * Wd : Wd;
     uint64_t total = n * B * per_scalar_entries;
     uint64_t nb = (1ull << (c - 1)) * G;  // total buckets
     // chunk size adapts to keep the window-sum stages wide: small MSMs (few
@@ -540,11 +569,7 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
     // digits+hist 0.63 ms with hot-counter atomics + scatter 1.60 ms of
     // uncoalesced atomic-cursor writes vs 0.04 + 0.86 for digits+sort;
     // cohort headline 1026 vs 1071 proofs/s) — kept for A/B re-checks.
-    static int binned_env = [] {
-        const char* e = getenv("RNG_MSM_BINNED");
-        return e ? atoi(e) : 0;
-    }();
-    const bool binned = binned_env && !glv;
+    const bool binned = msm_binned_enabled() && !glv && !fixed;
 
     uint32_t tb = 256;
     EvtTimer et;
@@ -639,6 +664,12 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
                            dim3(tb), 0, stream, s->glv, (uint32_t)n, c, W, B,
                            s->keys_in, s->vals_in);
         HIP_CHECK(hipGetLastError());
+    } else if (fixed) {
+        hipLaunchKernelGGL(k_msm_digits_fixed, dim3((uint32_t)((n * B + tb - 1) / tb)),
+                           dim3(tb), 0, stream, d_scalars, (uint32_t)n, c, Wd, B,
+                           (uint32_t)fixed_stride, s->keys_in, s->vals_in);
+        HIP_CHECK(hipGetLastError());
+        d_bases = d_fixed_table;  // bucket gathers index the window table
     } else {
         hipLaunchKernelGGL(k_msm_digits, dim3((uint32_t)((n * B + tb - 1) / tb)),
                            dim3(tb), 0, stream, d_scalars, (uint32_t)n, c, W, B,
@@ -646,15 +677,16 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
         HIP_CHECK(hipGetLastError());
     }
     et.mark(stream);
-    // sort only the live key bits: 16 magnitude bits + enough for G groups
-    // + the sentinel (G << 16); 3 radix passes instead of 4
+    // sort only the live key bits: the magnitude bits (16, or c in fixed-base
+    // mode) + enough for G groups + the sentinel (G << key_shift)
     uint32_t gb = 1;
     while ((1u << gb) <= G) ++gb;
+    const uint32_t sentinel = G << key_shift;
     rocprim::radix_sort_pairs(s->sort_temp, s->sort_temp_bytes, s->keys_in, s->keys_out,
-                              s->vals_in, s->vals_out, total, 0, 16 + gb, stream);
+                              s->vals_in, s->vals_out, total, 0, key_shift + gb, stream);
     HIP_CHECK(hipMemsetAsync(s->buckets, 0, nb * sizeof(G1Jac), stream));
     hipLaunchKernelGGL(k_msm_head_flags, dim3((uint32_t)((total + tb - 1) / tb)), dim3(tb),
-                       0, stream, s->keys_out, (uint32_t)total, msm_sentinel(G),
+                       0, stream, s->keys_out, (uint32_t)total, sentinel,
                        s->head_flags);
     HIP_CHECK(hipGetLastError());
     {
@@ -663,7 +695,7 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
                               s->heads, s->head_count, total, stream);
     }
     uint64_t max_heads = nb < total ? nb : total;
-    uint32_t seg_cap = msm_seg_cap(total);
+    uint32_t seg_cap = fixed ? msm_fixed_seg_cap(total) : msm_seg_cap(total);
     hipLaunchKernelGGL(k_msm_seg_lengths, dim3((uint32_t)((max_heads + tb - 1) / tb)),
                        dim3(tb), 0, stream, s->keys_out, s->heads, s->head_count,
                        (uint32_t)total, s->lens, s->nsub, seg_cap);
@@ -709,7 +741,7 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
         }
         hipLaunchKernelGGL(k_msm_seg_merge, dim3((hc + tb - 1) / tb), dim3(tb), 0,
                            stream, s->keys_out, s->heads, s->sub_off, s->nsub,
-                           s->head_order, hc, s->partials2, s->buckets, c);
+                           s->head_order, hc, s->partials2, s->buckets, c, key_shift);
         HIP_CHECK(hipGetLastError());
     } else {
         et.mark(stream);
@@ -736,9 +768,13 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
     uint32_t subb = 1;
     if (use_fold) {
         if ((uint64_t)G > s->window_sums_cap) {
+            // null + zero first: a failed hipMalloc must not leave a dangling
+            // pointer behind an inflated capacity
             hipFree(s->window_sums);
+            s->window_sums = nullptr;
+            s->window_sums_cap = 0;
+            HIP_CHECK(hipMalloc(&s->window_sums, (uint64_t)G * 2 * sizeof(G1Jac)));
             s->window_sums_cap = (uint64_t)G * 2;
-            HIP_CHECK(hipMalloc(&s->window_sums, s->window_sums_cap * sizeof(G1Jac)));
         }
         hipLaunchKernelGGL(k_msm_window_fold, dim3(G), dim3(cw), 0, stream,
                            s->buckets, c, chunk_sz, s->window_sums);
@@ -764,8 +800,10 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
             // big fused batches (cohort k=64: G=10240 groups) outgrow the
             // default window_sums allocation
             hipFree(s->window_sums);
+            s->window_sums = nullptr;
+            s->window_sums_cap = 0;
+            HIP_CHECK(hipMalloc(&s->window_sums, (uint64_t)G * subb * 2 * sizeof(G1Jac)));
             s->window_sums_cap = (uint64_t)G * subb * 2;
-            HIP_CHECK(hipMalloc(&s->window_sums, s->window_sums_cap * sizeof(G1Jac)));
         }
         static int msm_dbg = [] {
             const char* e = getenv("RNG_MSM_DEBUG");
@@ -821,6 +859,79 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
     else
         for (uint32_t b = 0; b < B; ++b) fold_one(b);
     return RNG_OK;
+}
+
+// ---- fixed-base MSM over the SRS ----
+// RNG_MSM_FIXED=0 restores the windowed (variable-base) path for A/B runs;
+// the GLV and binned A/B knobs also stay on the windowed path.
+static inline bool msm_fixed_enabled() {
+    static int v = [] {
+        const char* e = getenv("RNG_MSM_FIXED");
+        return e ? atoi(e) : 1;
+    }();
+    return v != 0 && !msm_glv_enabled() && !msm_binned_enabled();
+}
+
+// Window table for window size c, built on first use.  Returns nullptr when
+// no table is allowed (over 1 GiB, index past 31 bits, all three slots taken
+// by other window sizes) or the build failed; callers then fall back to the
+// windowed path.  Holds ctx->mu for the build and synchronizes before the
+// pointer is published, so concurrent cohort threads race to it safely.
+static const G1Aff* msm_fixed_table(RngCtxImpl* ctx, uint32_t c) {
+    const uint64_t N = ctx->srs_count;
+    const uint32_t W = (256 + c - 1) / c;
+    if (!ctx->srs_dev || N == 0 || c < 8 || c > 16) return nullptr;
+    if ((uint64_t)W * N * sizeof(G1Aff) > (1ull << 30) || ((uint64_t)W * N >> 31))
+        return nullptr;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    for (auto& t : ctx->fixed_tables)
+        if (t.dev && t.c == c) return (const G1Aff*)t.dev;
+    for (auto& t : ctx->fixed_tables) {
+        if (t.dev) continue;
+        void* dev = nullptr;
+        if (hipMalloc(&dev, (uint64_t)W * N * sizeof(G1Aff)) != hipSuccess) return nullptr;
+        hipLaunchKernelGGL(k_msm_fixed_table, dim3((uint32_t)((N + 255) / 256)), dim3(256),
+                           0, RNG_STREAM, (const G1Aff*)ctx->srs_dev, (uint32_t)N, c, W,
+                           (G1Aff*)dev);
+        if (hipGetLastError() != hipSuccess ||
+            hipStreamSynchronize(RNG_STREAM) != hipSuccess) {
+            hipFree(dev);
+            return nullptr;
+        }
+        t.c = c;
+        t.dev = dev;
+        return (const G1Aff*)dev;
+    }
+    return nullptr;
+}
+
+// Every SRS commitment goes through here: B polys of m canonical scalars
+// each (device) against the first m SRS points.  window_c 0 = auto (the
+// RNG_MSM_C tuning override applies); mode 0 = fixed-base where a table is
+// allowed, else windowed; 1 = fixed-base or error; 2 = windowed.
+static int msm_srs_run(RngCtxImpl* ctx, const uint64_t* d_canon, uint64_t m, uint32_t B,
+                       G1Jac* res, int window_c = 0, int mode = 0) {
+    if (m == 0 || m > ctx->srs_count || B == 0) return RNG_ERR_BAD_ARG;
+    static int c_env = [] {
+        const char* e = getenv("RNG_MSM_C");
+        return e ? atoi(e) : 0;
+    }();
+    if (window_c == 0 && c_env >= 8 && c_env <= 16) window_c = c_env;
+    if (window_c != 0 && (window_c < 8 || window_c > 16)) return RNG_ERR_BAD_ARG;
+    if (mode == 1 || (mode == 0 && msm_fixed_enabled())) {
+        uint32_t c = window_c ? (uint32_t)window_c : msm_fixed_c(m, B);
+        uint32_t gb = 1;
+        while ((1u << gb) <= B) ++gb;
+        const G1Aff* table = (c + gb <= 32) ? msm_fixed_table(ctx, c) : nullptr;
+        if (table)
+            return msm_dev_run((const G1Aff*)ctx->srs_dev, d_canon, m, c, res, B,
+                               RNG_STREAM, nullptr, table, ctx->srs_count);
+        if (mode == 1) return RNG_ERR_BAD_ARG;
+    }
+    uint32_t c = window_c ? (uint32_t)window_c : msm_auto_c(m);
+    if ((uint64_t)B * ((256 + c - 1) / c) > 60000) return RNG_ERR_BAD_ARG;  // g<<16 cap
+    return msm_dev_run((const G1Aff*)ctx->srs_dev, d_canon, m, c, res, B, RNG_STREAM,
+                       (const G1Aff*)ctx->srs_glv_dev);
 }
 
 // Jacobian (host) -> 9-u64 affine record, using host-side field ops.
@@ -957,13 +1068,7 @@ static int commit_dev_batch(RngCtxImpl* ctx, const std::vector<Fr>* const* polys
     HIP_CHECK(hipGetLastError());
     G1Jac res[13];
     // window size: auto by problem size; RNG_MSM_C overrides for tuning
-    static int c_env = [] {
-        const char* e = getenv("RNG_MSM_C");
-        return e ? atoi(e) : 0;
-    }();
-    uint32_t c_used = (c_env >= 8 && c_env <= 16) ? (uint32_t)c_env : msm_auto_c(m);
-    int rc = msm_dev_run((const G1Aff*)ctx->srs_dev, s->canon, m, c_used, res, B,
-                         RNG_STREAM, (const G1Aff*)ctx->srs_glv_dev);
+    int rc = msm_srs_run(ctx, s->canon, m, B, res);
     if (rc != RNG_OK) return rc;
     for (uint32_t b = 0; b < B; ++b) {
         uint64_t rec[9];
@@ -1104,17 +1209,8 @@ static int commit_staged(RngCtxImpl* ctx, uint64_t m, uint32_t B, G1Aff* out,
     hipLaunchKernelGGL(k_fr_to_canonical, dim3(blocks), dim3(256), 0, RNG_STREAM,
                        s->stage, s->canon, (uint32_t)(B * m));
     HIP_CHECK(hipGetLastError());
-    // bucket space per key group is 2^(c-1); it must stay well below the
-    // per-poly point count n or empty buckets dominate the fused batch
-    static int c_env = [] {
-        const char* e = getenv("RNG_MSM_C");
-        return e ? atoi(e) : 0;
-    }();
-    uint32_t c = (c_env >= 8 && c_env <= 16) ? (uint32_t)c_env : msm_auto_c(m);
-    if ((uint64_t)B * ((256 + c - 1) / c) > 60000) return RNG_ERR_BAD_ARG;  // g<<16 cap
     std::vector<G1Jac> res(B);
-    int rc = msm_dev_run((const G1Aff*)ctx->srs_dev, s->canon, m, c, res.data(), B,
-                         RNG_STREAM, (const G1Aff*)ctx->srs_glv_dev);
+    int rc = msm_srs_run(ctx, s->canon, m, B, res.data());
     if (rc != RNG_OK) return rc;
     HostPool::inst().parallel_for(B, [&](uint32_t b) {
         uint64_t rec[9];
@@ -2226,6 +2322,25 @@ int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,
     int rc = msm_dev_run((const G1Aff*)dev_bases, (const uint64_t*)dev_scalars, n, c, &res, 1);
     if (rc != RNG_OK) return rc;
     jac_to_affine_record(res, out9);
+    return RNG_OK;
+}
+
+int rng_msm_srs_batch(RngCtx* ctx, const uint64_t* scalars, uint64_t n, uint32_t B,
+                      int window_c, int mode, uint64_t* out9xB) {
+    if (!gpu_ok()) return RNG_ERR_NO_GPU;
+    if (!ctx || !scalars || !out9xB || n == 0 || B == 0 || mode < 0 || mode > 2)
+        return RNG_ERR_BAD_ARG;
+    void* ds = nullptr;
+    HIP_CHECK(hipMalloc(&ds, (uint64_t)B * n * 32));
+    std::vector<G1Jac> res(B);
+    int rc = RNG_OK;
+    if (hipMemcpy(ds, scalars, (uint64_t)B * n * 32, hipMemcpyHostToDevice) != hipSuccess)
+        rc = RNG_ERR_HIP;
+    if (rc == RNG_OK)
+        rc = msm_srs_run(&ctx->impl, (const uint64_t*)ds, n, B, res.data(), window_c, mode);
+    hipFree(ds);
+    if (rc != RNG_OK) return rc;
+    for (uint32_t b = 0; b < B; ++b) jac_to_affine_record(res[b], out9xB + 9 * b);
     return RNG_OK;
 }
 

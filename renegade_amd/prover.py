@@ -65,6 +65,9 @@ class ProverLib:
         self.lib.rng_msm_g1_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_uint64, _U64P,
                                             ctypes.c_int]
+        self.lib.rng_msm_srs_batch.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_uint64,
+                                               ctypes.c_uint32, ctypes.c_int,
+                                               ctypes.c_int, _U64P]
         self.lib.rng_srs_dev_bases.restype = ctypes.c_void_p
         self.lib.rng_srs_dev_bases.argtypes = [ctypes.c_void_p, _U64P]
 
@@ -142,6 +145,21 @@ class ProverCtx:
         self._check(self.lib.rng_msm_g1(self.h, _ptr(bases), _ptr(scalars), n, _ptr(out),
                                         window_c), "rng_msm_g1")
         return out
+
+    MSM_AUTO, MSM_FIXED_BASE, MSM_WINDOWED = 0, 1, 2
+
+    def msm_srs_batch(self, scalars: np.ndarray, n: int, batch: int = 1,
+                      window_c: int = 0, mode: int = 0):
+        """`batch` polynomials of n canonical scalars each (4*n*batch u64)
+        against the first n SRS points, through the prover's own commitment
+        MSM.  mode: MSM_AUTO / MSM_FIXED_BASE / MSM_WINDOWED.  Returns a
+        (batch, 9) array of affine records."""
+        assert scalars.dtype == np.uint64 and scalars.size == 4 * n * batch
+        scalars = np.ascontiguousarray(scalars).reshape(-1)
+        out = np.zeros(9 * batch, dtype=np.uint64)
+        self._check(self.lib.rng_msm_srs_batch(self.h, _ptr(scalars), n, batch, window_c,
+                                               mode, _ptr(out)), "rng_msm_srs_batch")
+        return out.reshape(batch, 9)
 
     # ---- device-resident helpers (benchmarking) ----
     def dbuf_from(self, host: np.ndarray):
