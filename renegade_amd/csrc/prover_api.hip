@@ -230,7 +230,6 @@ struct RngCtxImpl {
     std::vector<uint64_t> srs_g1_host;  // (max_degree+1) * 8 u64 packed affine
     uint64_t srs_count = 0;
     void* srs_dev = nullptr;
-    void* srs_glv_dev = nullptr;  // [P, phi(P)] interleaved for GLV
     // fixed-base window tables T[j*srs_count + i] = 2^(c*j) * P_i, built
     // lazily per window size c (msm_fixed_c returns at most three values)
     struct FixedTable {
@@ -252,7 +251,6 @@ struct RngCtxImpl {
                 hip_free_guarded(b);
         }
         hip_free_guarded(srs_dev);
-        hip_free_guarded(srs_glv_dev);
         for (auto& t : fixed_tables) hip_free_guarded(t.dev);
     }
 };
@@ -384,6 +382,117 @@ static int ntt_dev_run(RngCtxImpl* ctx, Fr* data, Fr* out, uint32_t n, uint64_t 
 
 // ---------------- MSM ----------------
 
+// The RNG_MSM_* variables, read once per process.  RNG_MSM_FIXED=0 sends
+// SRS commitments down the windowed path for A/B runs; the others are
+// tuning overrides that apply only inside the range given (0 = unset).
+struct MsmEnv {
+    int fixed;    // RNG_MSM_FIXED, default 1
+    int c;        // RNG_MSM_C 8..16: window size, only where window_c == 0
+    int chunk;    // RNG_MSM_CHUNK 2..16: buckets per window-sum lane
+    int subb;     // RNG_MSM_SUBB 1..256: combine sub-blocks per key group
+    int seg_cap;  // RNG_MSM_SEGCAP 8..MSM_MAX_SEG: fixed-base sub-segment cap
+    int debug;    // RNG_MSM_DEBUG: one stderr line per MSM
+};
+
+static const MsmEnv& msm_env() {
+    static const MsmEnv env = [] {
+        auto get = [](const char* name, int unset) {
+            const char* e = getenv(name);
+            return e ? atoi(e) : unset;
+        };
+        return MsmEnv{get("RNG_MSM_FIXED", 1),  get("RNG_MSM_C", 0),
+                      get("RNG_MSM_CHUNK", 0),  get("RNG_MSM_SUBB", 0),
+                      get("RNG_MSM_SEGCAP", 0), get("RNG_MSM_DEBUG", 0)};
+    }();
+    return env;
+}
+
+// What an MSM gathers its points from: a plain base array (windowed
+// Pippenger, one bucket set per (poly, window)), or the fixed-base window
+// table T[j*stride + i] = 2^(c*j) * P_i built for this c (every digit
+// gathers its own pre-weighted point, so a poly's W digit positions share
+// ONE bucket set and the fold sees a single "window").
+struct MsmBases {
+    const G1Aff* points;    // base array, or the window table
+    uint64_t table_stride;  // 0 = plain base array; else the table's row length N
+    static MsmBases plain(const G1Aff* bases) { return {bases, 0}; }
+    static MsmBases table(const G1Aff* t, uint64_t stride) { return {t, stride}; }
+    bool fixed() const { return table_stride != 0; }
+};
+
+// Every size of one MSM call: B polys of n scalars at window size c.
+struct MsmShape {
+    uint64_t n;
+    uint32_t B, c;
+    bool fixed;
+    uint32_t Wd;         // digit positions per scalar
+    uint32_t W;          // windows per poly as seen by buckets/aggregation/fold
+    uint32_t G;          // key groups
+    uint32_t key_shift;  // keys pack group << key_shift | magnitude
+    uint64_t total;      // digit entries
+    uint64_t nb;         // buckets
+    uint32_t chunk_sz;   // buckets per window-sum lane
+    uint64_t nchunks;
+    uint32_t cw;         // chunks per key group
+    uint32_t subb;       // combine sub-blocks per key group
+    uint32_t seg_cap;    // longest sub-segment one reduce lane walks
+    uint32_t sentinel;   // key of a zero digit
+    uint32_t sort_bits;  // live key bits
+};
+
+static MsmShape msm_shape(uint64_t n, uint32_t B, uint32_t c, bool fixed) {
+    const MsmEnv& env = msm_env();
+    MsmShape sh;
+    sh.n = n;
+    sh.B = B;
+    sh.c = c;
+    sh.fixed = fixed;
+    sh.Wd = (256 + c - 1) / c;
+    sh.W = fixed ? 1 : sh.Wd;
+    sh.G = B * sh.W;
+    // the fixed mode packs tightly (magnitude <= 2^(c-1) needs c bits) so the
+    // sort touches c + gb bits
+    sh.key_shift = fixed ? c : 16;
+    sh.total = n * B * sh.Wd;
+    sh.nb = (1ull << (c - 1)) * sh.G;
+    // chunk size adapts to keep the window-sum stages wide: small MSMs (few
+    // windows x small bucket counts) get chunk=2 (4x the lanes, 4x shorter
+    // latency chains), the 2^20 leg keeps chunk=16.
+    // target >=128k lanes: the per-chunk suffix walk is a serial EC chain, so
+    // the chunk kernel is latency-bound until the chip is several waves deep
+    // per SIMD (r02: chunk 16 -> 4 at 2^20 cut window_chunks ~3x)
+    sh.chunk_sz = MSM_CHUNK;
+    while (sh.chunk_sz > 2 && sh.nb / sh.chunk_sz < 131072) sh.chunk_sz >>= 1;
+    if (env.chunk >= 2 && env.chunk <= 16) sh.chunk_sz = (uint32_t)env.chunk;
+    if ((1u << (c - 1)) < sh.chunk_sz) sh.chunk_sz = 1u << (c - 1);
+    sh.nchunks = ((1ull << (c - 1)) / sh.chunk_sz) * sh.G;
+    sh.cw = (1u << (c - 1)) / sh.chunk_sz;
+    // sub-blocks per window: enough blocks to spread chunks, but never more
+    // than chunks (idle blocks)
+    sh.subb = MSM_SUBB;
+    while (sh.subb > 1 && sh.cw / sh.subb < 64) sh.subb >>= 1;
+    // the combine blocks are serial EC chains: push toward >=2048 waves
+    // (1 block = 1 wave of 64 lanes) while keeping >=64 chunks per block
+    // so the scan-based combine2 applies
+    while (sh.subb < 256 && sh.G * sh.subb < 4096 && sh.cw / (2 * sh.subb) >= 64 &&
+           (uint64_t)sh.G * sh.subb * 2 <= 8192)
+        sh.subb <<= 1;
+    if (env.subb >= 1 && env.subb <= 256) sh.subb = (uint32_t)env.subb;
+    // fixed-base mode: a bucket holds n*W/2^(c-1) entries (W times the
+    // windowed path's), so the cap trades bucket-reduce lanes against
+    // Jacobian adds in k_msm_seg_merge; only there does the override apply
+    sh.seg_cap = msm_seg_cap(sh.total);
+    if (fixed && env.seg_cap >= 8 && env.seg_cap <= (int)MSM_MAX_SEG)
+        sh.seg_cap = (uint32_t)env.seg_cap;
+    // sort only the live key bits: the magnitude bits (16, or c in fixed-base
+    // mode) + enough for G groups + the sentinel (G << key_shift)
+    uint32_t gb = 1;
+    while ((1u << gb) <= sh.G) ++gb;
+    sh.sentinel = sh.G << sh.key_shift;
+    sh.sort_bits = sh.key_shift + gb;
+    return sh;
+}
+
 struct MsmScratch {
     uint32_t *keys_in = nullptr, *keys_out = nullptr, *vals_in = nullptr, *vals_out = nullptr;
     void* sort_temp = nullptr;
@@ -405,18 +514,11 @@ struct MsmScratch {
     size_t select_temp_bytes = 0;
     void* scan_temp = nullptr;
     size_t scan_temp_bytes = 0;
-    // binned (counting-scatter) pipeline
-    uint32_t* counts = nullptr;   // nb
-    uint32_t* offsets = nullptr;  // nb
-    uint32_t* cursor = nullptr;   // nb
-    uint8_t* bflags = nullptr;    // nb
     G1Jac* buckets = nullptr;
     G1Jac* partials = nullptr;
     G1Jac* window_sums = nullptr;
     uint64_t window_sums_cap = 0;  // entries (G*subb grows with fused B)
     G1Jac* result = nullptr;
-    uint64_t* glv = nullptr;   // per-scalar (k1, k2) magnitudes + signs
-    G1Aff* phi = nullptr;      // phi(bases) scratch for non-SRS base arrays
     uint64_t cap_entries = 0;
     uint64_t cap_nb = 0;
     uint64_t cap_nchunks = 0;
@@ -429,87 +531,23 @@ struct MsmScratch {
                         (void*)nsub_sorted, (void*)head_order,
                         (void*)partials2, (void*)head_count, select_temp, scan_temp,
                         (void*)buckets, (void*)partials, (void*)window_sums,
-                        (void*)result, (void*)glv, (void*)phi, (void*)counts,
-                        (void*)offsets, (void*)cursor, (void*)bflags})
+                        (void*)result})
             hip_free_guarded(b);
     }
 };
 
 static thread_local std::unique_ptr<MsmScratch> tls_msm_scratch;
 
-// B polynomials sharing one base array -> one fused pipeline; results[B].
-// GLV endomorphism path (RNG_MSM_GLV=1): bit-exact (parity-green) but OFF
-// by default — measured on MI355X the halved aggregation does not pay for
-// the decompose + doubled digit work at proof sizes (335 vs 387 proofs/s)
-// or at 2^20 (7.4 vs 6.3 ms); see DESIGN.md §4.1.
-static inline bool msm_glv_enabled() {
-    static int v = [] {
-        const char* e = getenv("RNG_MSM_GLV");
-        return e ? atoi(e) : 0;
-    }();
-    return v != 0;
-}
-
-static inline bool msm_binned_enabled() {
-    static int v = [] {
-        const char* e = getenv("RNG_MSM_BINNED");
-        return e ? atoi(e) : 0;
-    }();
-    return v != 0;
-}
-
-static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t n,
-                       uint32_t c, G1Jac* h_result, uint32_t B = 1,
-                       hipStream_t stream = RNG_STREAM,
-                       const G1Aff* d_glv_bases = nullptr,
-                       const G1Aff* d_fixed_table = nullptr,
-                       uint64_t fixed_stride = 0) {
-    // fixed-base mode (d_fixed_table = window table for this c, fixed_stride =
-    // its row length N): every digit gathers its own pre-weighted table point,
-    // so a poly's W digit positions share ONE bucket set (key group = poly)
-    // and the fold below sees a single "window".  Callers pass a table only
-    // when neither RNG_MSM_GLV nor RNG_MSM_BINNED is set (msm_srs_run).
-    const bool fixed = d_fixed_table != nullptr;
-    const bool glv = !fixed && msm_glv_enabled();
-    // GLV halves scalar width: two 127-bit halves share each window's buckets
-    uint32_t W = glv ? (128 + c - 1) / c : (256 + c - 1) / c;
-    const uint32_t Wd = W;  // digit positions per scalar
-    if (fixed) W = 1;       // windows per poly as seen by buckets/aggregation/fold
-    uint32_t G = B * W;  // key groups
-    // keys pack group << key_shift | magnitude; the fixed mode packs tightly
-    // (magnitude <= 2^(c-1) needs c bits) so the sort touches c + gb bits
-    const uint32_t key_shift = fixed ? c : 16;
-    uint64_t per_scalar_entries = glv ? 2 * Wd : Wd;
-    uint64_t total = n * B * per_scalar_entries;
-    uint64_t nb = (1ull << (c - 1)) * G;  // total buckets
-    // chunk size adapts to keep the window-sum stages wide: small MSMs (few
-    // windows x small bucket counts) get chunk=2 (4x the lanes, 4x shorter
-    // latency chains), the 2^20 leg keeps chunk=16.
-    uint32_t chunk_sz = MSM_CHUNK;
-    {
-        uint64_t nbw = (1ull << (c - 1)) * G;
-        // target >=128k lanes: the per-chunk suffix walk is a serial EC
-        // chain, so the chunk kernel is latency-bound until the chip is
-        // several waves deep per SIMD (r02: chunk 16 -> 4 at 2^20 cut
-        // window_chunks ~3x)
-        while (chunk_sz > 2 && nbw / chunk_sz < 131072) chunk_sz >>= 1;
-        static int chunk_env = [] {
-            const char* e = getenv("RNG_MSM_CHUNK");
-            return e ? atoi(e) : 0;
-        }();
-        if (chunk_env >= 2 && chunk_env <= 16) chunk_sz = (uint32_t)chunk_env;
-        if ((1u << (c - 1)) < chunk_sz) chunk_sz = 1u << (c - 1);
-    }
-    uint64_t nchunks = ((1ull << (c - 1)) / chunk_sz) * G;
-
+// The calling thread's scratch, grown to hold `sh`.
+static int msm_scratch_ensure(const MsmShape& sh, hipStream_t stream, MsmScratch** out) {
     if (!tls_msm_scratch) tls_msm_scratch = std::make_unique<MsmScratch>();
     MsmScratch* s = tls_msm_scratch.get();
-    if (s->cap_entries < total || s->cap_nb < nb || s->cap_nchunks < nchunks) {
+    if (s->cap_entries < sh.total || s->cap_nb < sh.nb || s->cap_nchunks < sh.nchunks) {
         // size with 1.5x slack so nearby problem sizes (n, n+2, n+3 commits,
         // different auto window sizes) never thrash device allocations
-        uint64_t cap_total = total + total / 2 + 64;
-        uint64_t cap_nb2 = nb + nb / 2 + 64;
-        uint64_t cap_nch = nchunks + nchunks / 2 + 64;
+        uint64_t cap_total = sh.total + sh.total / 2 + 64;
+        uint64_t cap_nb2 = sh.nb + sh.nb / 2 + 64;
+        uint64_t cap_nch = sh.nchunks + sh.nchunks / 2 + 64;
         tls_msm_scratch = std::make_unique<MsmScratch>();
         s = tls_msm_scratch.get();
         HIP_CHECK(hipMalloc(&s->keys_in, cap_total * 4));
@@ -546,296 +584,145 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
                                           rocprim::plus<uint32_t>(), stream);
             HIP_CHECK(hipMalloc(&s->scan_temp, s->scan_temp_bytes));
         }
-        HIP_CHECK(hipMalloc(&s->counts, cap_nb2 * 4));
-        HIP_CHECK(hipMalloc(&s->offsets, cap_nb2 * 4));
-        HIP_CHECK(hipMalloc(&s->cursor, cap_nb2 * 4));
-        HIP_CHECK(hipMalloc(&s->bflags, cap_nb2));
         HIP_CHECK(hipMalloc(&s->buckets, cap_nb2 * sizeof(G1Jac)));
         HIP_CHECK(hipMalloc(&s->partials, 2 * cap_nch * sizeof(G1Jac)));
         HIP_CHECK(hipMalloc(&s->window_sums, 512 * MSM_SUBB * sizeof(G1Jac)));
         s->window_sums_cap = 512 * MSM_SUBB;
         HIP_CHECK(hipMalloc(&s->result, sizeof(G1Jac)));
-        // glv: 32 B per scalar = 16*total/W bytes <= 2*total (W >= 8)
-        HIP_CHECK(hipMalloc(&s->glv, 2 * cap_total));
-        // phi: 64 B per base = 32*total/(W*B) bytes <= 4*total (W >= 8, B >= 1)
-        HIP_CHECK(hipMalloc(&s->phi, 4 * cap_total));
         s->cap_entries = cap_total;
         s->cap_nb = cap_nb2;
         s->cap_nchunks = cap_nch;
     }
-
-    // binned (counting-scatter) pipeline, RNG_MSM_BINNED=1 to enable.
-    // Measured SLOWER than the rocPRIM onesweep sort on MI355X (2^20 MSM:
-    // digits+hist 0.63 ms with hot-counter atomics + scatter 1.60 ms of
-    // uncoalesced atomic-cursor writes vs 0.04 + 0.86 for digits+sort;
-    // cohort headline 1026 vs 1071 proofs/s) — kept for A/B re-checks.
-    const bool binned = msm_binned_enabled() && !glv && !fixed;
-
-    uint32_t tb = 256;
-    EvtTimer et;
-    et.mark(stream);
-    if (binned) {
-        HIP_CHECK(hipMemsetAsync(s->counts, 0, nb * 4, stream));
-        hipLaunchKernelGGL(k_msm_digits_hist, dim3((uint32_t)((n * B + tb - 1) / tb)),
-                           dim3(tb), 0, stream, d_scalars, (uint32_t)n, c, W, B,
-                           s->keys_in, s->vals_in, s->counts);
-        HIP_CHECK(hipGetLastError());
-        et.mark(stream);
-        (void)rocprim::exclusive_scan(s->scan_temp, s->scan_temp_bytes, s->counts,
-                                      s->offsets, 0u, nb, rocprim::plus<uint32_t>(),
-                                      stream);
-        HIP_CHECK(hipMemcpyAsync(s->cursor, s->offsets, nb * 4,
-                                 hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(k_msm_scatter, dim3((uint32_t)((total + tb - 1) / tb)),
-                           dim3(tb), 0, stream, s->keys_in, s->vals_in, total,
-                           s->cursor, s->vals_out);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemsetAsync(s->buckets, 0, nb * sizeof(G1Jac), stream));
-        hipLaunchKernelGGL(k_nonzero_flags, dim3((uint32_t)((nb + tb - 1) / tb)),
-                           dim3(tb), 0, stream, s->counts, (uint32_t)nb, s->bflags);
-        HIP_CHECK(hipGetLastError());
-        {
-            // keys_out holds the compacted non-empty bucket ids
-            rocprim::counting_iterator<uint32_t> cit(0);
-            (void)rocprim::select(s->select_temp, s->select_temp_bytes, cit, s->bflags,
-                                  s->keys_out, s->head_count, nb, stream);
-        }
-        uint32_t seg_cap = msm_seg_cap(total);
-        hipLaunchKernelGGL(k_msm_seg_from_counts, dim3((uint32_t)((nb + tb - 1) / tb)),
-                           dim3(tb), 0, stream, s->keys_out, s->offsets, s->counts,
-                           s->head_count, s->heads, s->lens, s->nsub, seg_cap);
-        HIP_CHECK(hipGetLastError());
-        uint32_t hc = 0;
-        HIP_CHECK(hipMemcpyAsync(&hc, s->head_count, 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        if (hc > 0) {
-            (void)rocprim::exclusive_scan(s->scan_temp, s->scan_temp_bytes, s->nsub,
-                                          s->sub_off, 0u, hc, rocprim::plus<uint32_t>(),
-                                          stream);
-            uint32_t last_off = 0, last_n = 0;
-            HIP_CHECK(hipMemcpyAsync(&last_off, s->sub_off + hc - 1, 4,
-                                     hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipMemcpyAsync(&last_n, s->nsub + hc - 1, 4,
-                                     hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            uint32_t sub_total = last_off + last_n;
-            hipLaunchKernelGGL(k_msm_make_subs, dim3((hc + tb - 1) / tb), dim3(tb), 0,
-                               stream, s->heads, s->lens, s->sub_off, s->head_count,
-                               s->sub_start, s->sub_len, seg_cap);
-            HIP_CHECK(hipGetLastError());
-            {
-                rocprim::counting_iterator<uint32_t> cit(0);
-                rocprim::radix_sort_pairs_desc(s->sort_temp, s->sort_temp_bytes,
-                                               s->sub_len, s->sub_len_sorted, cit,
-                                               s->sub_order, sub_total, 0, 8, stream);
-            }
-            et.mark(stream);
-            hipLaunchKernelGGL(k_msm_bucket_reduce, dim3((sub_total + tb - 1) / tb),
-                               dim3(tb), 0, stream, s->vals_out, s->sub_start,
-                               s->sub_len, s->sub_order, sub_total, d_bases,
-                               s->partials2);
-            HIP_CHECK(hipGetLastError());
-            {
-                rocprim::counting_iterator<uint32_t> cit(0);
-                rocprim::radix_sort_pairs_desc(s->sort_temp, s->sort_temp_bytes,
-                                               s->nsub, s->nsub_sorted, cit,
-                                               s->head_order, hc, 0, 16, stream);
-            }
-            hipLaunchKernelGGL(k_msm_seg_merge2, dim3((hc + tb - 1) / tb), dim3(tb), 0,
-                               stream, s->keys_out, s->sub_off, s->nsub, s->head_order,
-                               hc, s->partials2, s->buckets);
-            HIP_CHECK(hipGetLastError());
-        } else {
-            et.mark(stream);
-        }
-    } else {  // radix-sort path (GLV, or RNG_MSM_BINNED=0)
-    if (glv) {
-        if (!d_glv_bases) {  // non-SRS bases: interleave into scratch
-            hipLaunchKernelGGL(k_bases_interleave, dim3((uint32_t)((n + tb - 1) / tb)),
-                               dim3(tb), 0, stream, d_bases, s->phi, (uint32_t)n);
-            HIP_CHECK(hipGetLastError());
-            d_glv_bases = s->phi;
-        }
-        d_bases = d_glv_bases;  // bucket gathers index the interleaved array
-        hipLaunchKernelGGL(k_glv_decompose, dim3((uint32_t)((n * B + tb - 1) / tb)),
-                           dim3(tb), 0, stream, d_scalars, (uint32_t)(n * B), s->glv);
-        HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_msm_digits_glv, dim3((uint32_t)((n * B + tb - 1) / tb)),
-                           dim3(tb), 0, stream, s->glv, (uint32_t)n, c, W, B,
-                           s->keys_in, s->vals_in);
-        HIP_CHECK(hipGetLastError());
-    } else if (fixed) {
-        hipLaunchKernelGGL(k_msm_digits_fixed, dim3((uint32_t)((n * B + tb - 1) / tb)),
-                           dim3(tb), 0, stream, d_scalars, (uint32_t)n, c, Wd, B,
-                           (uint32_t)fixed_stride, s->keys_in, s->vals_in);
-        HIP_CHECK(hipGetLastError());
-        d_bases = d_fixed_table;  // bucket gathers index the window table
-    } else {
-        hipLaunchKernelGGL(k_msm_digits, dim3((uint32_t)((n * B + tb - 1) / tb)),
-                           dim3(tb), 0, stream, d_scalars, (uint32_t)n, c, W, B,
-                           s->keys_in, s->vals_in);
-        HIP_CHECK(hipGetLastError());
+    if ((uint64_t)sh.G * sh.subb > s->window_sums_cap) {
+        // big fused batches (cohort k=64: G=10240 groups) outgrow the default
+        // window_sums allocation.  null + zero first: a failed hipMalloc must
+        // not leave a dangling pointer behind an inflated capacity
+        hipFree(s->window_sums);
+        s->window_sums = nullptr;
+        s->window_sums_cap = 0;
+        HIP_CHECK(hipMalloc(&s->window_sums, (uint64_t)sh.G * sh.subb * 2 * sizeof(G1Jac)));
+        s->window_sums_cap = (uint64_t)sh.G * sh.subb * 2;
     }
+    *out = s;
+    return RNG_OK;
+}
+
+// Stage 1: digits -> radix sort -> segment heads -> capped sub-segments ->
+// reduce -> merge.  Leaves one Jacobian per bucket in s->buckets.
+static int msm_bucket_sums(const MsmShape& sh, const MsmBases& bases,
+                           const uint64_t* d_scalars, MsmScratch* s, EvtTimer& et,
+                           hipStream_t stream) {
+    const uint32_t tb = 256;
+    const uint32_t c = sh.c, total = (uint32_t)sh.total;
+    const dim3 scalar_grid((uint32_t)((sh.n * sh.B + tb - 1) / tb));
+    if (sh.fixed)
+        hipLaunchKernelGGL(k_msm_digits_fixed, scalar_grid, dim3(tb), 0, stream, d_scalars,
+                           (uint32_t)sh.n, c, sh.Wd, sh.B, (uint32_t)bases.table_stride,
+                           s->keys_in, s->vals_in);
+    else
+        hipLaunchKernelGGL(k_msm_digits, scalar_grid, dim3(tb), 0, stream, d_scalars,
+                           (uint32_t)sh.n, c, sh.Wd, sh.B, s->keys_in, s->vals_in);
+    HIP_CHECK(hipGetLastError());
     et.mark(stream);
-    // sort only the live key bits: the magnitude bits (16, or c in fixed-base
-    // mode) + enough for G groups + the sentinel (G << key_shift)
-    uint32_t gb = 1;
-    while ((1u << gb) <= G) ++gb;
-    const uint32_t sentinel = G << key_shift;
     rocprim::radix_sort_pairs(s->sort_temp, s->sort_temp_bytes, s->keys_in, s->keys_out,
-                              s->vals_in, s->vals_out, total, 0, key_shift + gb, stream);
-    HIP_CHECK(hipMemsetAsync(s->buckets, 0, nb * sizeof(G1Jac), stream));
-    hipLaunchKernelGGL(k_msm_head_flags, dim3((uint32_t)((total + tb - 1) / tb)), dim3(tb),
-                       0, stream, s->keys_out, (uint32_t)total, sentinel,
-                       s->head_flags);
+                              s->vals_in, s->vals_out, sh.total, 0, sh.sort_bits, stream);
+    HIP_CHECK(hipMemsetAsync(s->buckets, 0, sh.nb * sizeof(G1Jac), stream));
+    hipLaunchKernelGGL(k_msm_head_flags, dim3((uint32_t)((sh.total + tb - 1) / tb)),
+                       dim3(tb), 0, stream, s->keys_out, total, sh.sentinel, s->head_flags);
     HIP_CHECK(hipGetLastError());
     {
         rocprim::counting_iterator<uint32_t> cit(0);
         (void)rocprim::select(s->select_temp, s->select_temp_bytes, cit, s->head_flags,
-                              s->heads, s->head_count, total, stream);
+                              s->heads, s->head_count, sh.total, stream);
     }
-    uint64_t max_heads = nb < total ? nb : total;
-    uint32_t seg_cap = fixed ? msm_fixed_seg_cap(total) : msm_seg_cap(total);
+    uint64_t max_heads = sh.nb < sh.total ? sh.nb : sh.total;
     hipLaunchKernelGGL(k_msm_seg_lengths, dim3((uint32_t)((max_heads + tb - 1) / tb)),
-                       dim3(tb), 0, stream, s->keys_out, s->heads, s->head_count,
-                       (uint32_t)total, s->lens, s->nsub, seg_cap);
+                       dim3(tb), 0, stream, s->keys_out, s->heads, s->head_count, total,
+                       s->lens, s->nsub, sh.seg_cap);
     HIP_CHECK(hipGetLastError());
     uint32_t hc = 0;
     HIP_CHECK(hipMemcpyAsync(&hc, s->head_count, 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    if (hc > 0) {
-        // sub-segment split (caps any lane's walk at MSM_MAX_SEG entries)
-        (void)rocprim::exclusive_scan(s->scan_temp, s->scan_temp_bytes, s->nsub,
-                                      s->sub_off, 0u, hc, rocprim::plus<uint32_t>(),
-                                      stream);
-        uint32_t last_off = 0, last_n = 0;
-        HIP_CHECK(hipMemcpyAsync(&last_off, s->sub_off + hc - 1, 4,
-                                 hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipMemcpyAsync(&last_n, s->nsub + hc - 1, 4, hipMemcpyDeviceToHost,
-                                 stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        uint32_t sub_total = last_off + last_n;
-        hipLaunchKernelGGL(k_msm_make_subs, dim3((hc + tb - 1) / tb), dim3(tb), 0,
-                           stream, s->heads, s->lens, s->sub_off, s->head_count,
-                           s->sub_start, s->sub_len, seg_cap);
-        HIP_CHECK(hipGetLastError());
-        {
-            // order subs by length desc so each wave's lanes walk equal work
-            rocprim::counting_iterator<uint32_t> cit(0);
-            rocprim::radix_sort_pairs_desc(s->sort_temp, s->sort_temp_bytes, s->sub_len,
-                                           s->sub_len_sorted, cit, s->sub_order,
-                                           sub_total, 0, 8, stream);
-        }
+    if (hc == 0) {  // every digit zero: the zeroed buckets are the answer
         et.mark(stream);
-        hipLaunchKernelGGL(k_msm_bucket_reduce, dim3((sub_total + tb - 1) / tb), dim3(tb),
-                           0, stream, s->vals_out, s->sub_start, s->sub_len, s->sub_order,
-                           sub_total, d_bases, s->partials2);
-        HIP_CHECK(hipGetLastError());
-        {
-            // order heads by sub count desc: the handful of long-merge heads
-            // (top-window buckets) otherwise serialize whole waves
-            rocprim::counting_iterator<uint32_t> cit(0);
-            rocprim::radix_sort_pairs_desc(s->sort_temp, s->sort_temp_bytes, s->nsub,
-                                           s->nsub_sorted, cit, s->head_order, hc, 0,
-                                           16, stream);
-        }
-        hipLaunchKernelGGL(k_msm_seg_merge, dim3((hc + tb - 1) / tb), dim3(tb), 0,
-                           stream, s->keys_out, s->heads, s->sub_off, s->nsub,
-                           s->head_order, hc, s->partials2, s->buckets, c, key_shift);
-        HIP_CHECK(hipGetLastError());
-    } else {
         et.mark(stream);
+        return RNG_OK;
     }
-    }  // end radix-sort path
-    et.mark(stream);
-    uint32_t cw = (1u << (c - 1)) / chunk_sz;
-    // fused suffix-scan fold (k_msm_window_fold) measured SLOWER than the
-    // chunk+combine pair at proof sizes (368 vs 402 proofs/s): Hillis-Steele
-    // does a full-width EC add per lane per level and each level carries a
-    // barrier + LDS Jacobian traffic; kept behind RNG_MSM_FOLD=1.
-    static int fold_env = [] {
-        const char* e = getenv("RNG_MSM_FOLD");
-        return e ? atoi(e) : 0;
-    }();
-    bool use_fold = fold_env && cw <= 256;
-    if (!use_fold) {  // separate chunk pass feeding the combine
-        hipLaunchKernelGGL(k_msm_window_chunks,
-                           dim3((uint32_t)((nchunks + tb - 1) / tb)), dim3(tb), 0,
-                           stream, s->buckets, c, G, chunk_sz, s->partials);
-        HIP_CHECK(hipGetLastError());
-    }
-    et.mark(stream);
-    uint32_t subb = 1;
-    if (use_fold) {
-        if ((uint64_t)G > s->window_sums_cap) {
-            // null + zero first: a failed hipMalloc must not leave a dangling
-            // pointer behind an inflated capacity
-            hipFree(s->window_sums);
-            s->window_sums = nullptr;
-            s->window_sums_cap = 0;
-            HIP_CHECK(hipMalloc(&s->window_sums, (uint64_t)G * 2 * sizeof(G1Jac)));
-            s->window_sums_cap = (uint64_t)G * 2;
-        }
-        hipLaunchKernelGGL(k_msm_window_fold, dim3(G), dim3(cw), 0, stream,
-                           s->buckets, c, chunk_sz, s->window_sums);
-        HIP_CHECK(hipGetLastError());
-        et.mark(stream);
-    } else {
-        // sub-blocks per window: enough blocks to spread chunks, but never
-        // more than chunks (idle blocks); RNG_MSM_SUBB overrides for tuning
-        subb = MSM_SUBB;
-        while (subb > 1 && cw / subb < 64) subb >>= 1;
-        // the combine blocks are serial EC chains: push toward >=2048 waves
-        // (1 block = 1 wave of 64 lanes) while keeping >=64 chunks per block
-        // so the scan-based combine2 applies
-        while (subb < 256 && G * subb < 4096 && cw / (2 * subb) >= 64 &&
-               (uint64_t)G * subb * 2 <= 8192)
-            subb <<= 1;
-        static int subb_env = [] {
-            const char* e = getenv("RNG_MSM_SUBB");
-            return e ? atoi(e) : 0;
-        }();
-        if (subb_env >= 1 && subb_env <= 256) subb = (uint32_t)subb_env;
-        if ((uint64_t)G * subb > s->window_sums_cap) {
-            // big fused batches (cohort k=64: G=10240 groups) outgrow the
-            // default window_sums allocation
-            hipFree(s->window_sums);
-            s->window_sums = nullptr;
-            s->window_sums_cap = 0;
-            HIP_CHECK(hipMalloc(&s->window_sums, (uint64_t)G * subb * 2 * sizeof(G1Jac)));
-            s->window_sums_cap = (uint64_t)G * subb * 2;
-        }
-        static int msm_dbg = [] {
-            const char* e = getenv("RNG_MSM_DEBUG");
-            return e ? atoi(e) : 0;
-        }();
-        if (msm_dbg)
-            fprintf(stderr, "[msm] n=%lu B=%u c=%u chunk=%u cw=%u subb=%u combine=%s\n",
-                    (unsigned long)n, B, c, chunk_sz, cw, subb,
-                    (cw % subb == 0 && (cw / subb) % 64 == 0) ? "scan2" : "v1");
-        if (cw % subb == 0 && (cw / subb) % 64 == 0) {
-            // scan-based combine: no per-chunk scalar weights
-            hipLaunchKernelGGL(k_msm_window_combine2, dim3(G * subb), dim3(64), 0,
-                               stream, s->partials, c, chunk_sz, subb,
-                               s->window_sums);
-        } else {
-            hipLaunchKernelGGL(k_msm_window_combine, dim3(G * subb), dim3(64), 0,
-                               stream, s->partials, c, chunk_sz, subb,
-                               s->window_sums);
-        }
-        HIP_CHECK(hipGetLastError());
-        et.mark(stream);
-    }
-    // host-side fold: G*SUBB Jacobians; a single-lane dependent EC chain is
-    // far faster on a host core than on one GPU lane
-    std::vector<G1Jac> wsums((size_t)G * subb);
-    HIP_CHECK(hipMemcpyAsync(wsums.data(), s->window_sums, G * subb * sizeof(G1Jac),
-                             hipMemcpyDeviceToHost, stream));
+    // sub-segment split (caps any lane's walk at seg_cap entries)
+    (void)rocprim::exclusive_scan(s->scan_temp, s->scan_temp_bytes, s->nsub, s->sub_off, 0u,
+                                  hc, rocprim::plus<uint32_t>(), stream);
+    uint32_t last_off = 0, last_n = 0;
+    HIP_CHECK(hipMemcpyAsync(&last_off, s->sub_off + hc - 1, 4, hipMemcpyDeviceToHost,
+                             stream));
+    HIP_CHECK(hipMemcpyAsync(&last_n, s->nsub + hc - 1, 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    et.collect(tls_msm_times, 5);
-    // two pooled stages: per-(poly, window) sub-block reduction, then the
-    // per-poly Horner across windows (the window count is small; a serial
-    // 1024-add fold on one core showed up at B=1 with wide subb)
+    uint32_t sub_total = last_off + last_n;
+    hipLaunchKernelGGL(k_msm_make_subs, dim3((hc + tb - 1) / tb), dim3(tb), 0, stream,
+                       s->heads, s->lens, s->sub_off, s->head_count, s->sub_start,
+                       s->sub_len, sh.seg_cap);
+    HIP_CHECK(hipGetLastError());
+    {
+        // order subs by length desc so each wave's lanes walk equal work
+        rocprim::counting_iterator<uint32_t> cit(0);
+        rocprim::radix_sort_pairs_desc(s->sort_temp, s->sort_temp_bytes, s->sub_len,
+                                       s->sub_len_sorted, cit, s->sub_order, sub_total, 0,
+                                       8, stream);
+    }
+    et.mark(stream);
+    hipLaunchKernelGGL(k_msm_bucket_reduce, dim3((sub_total + tb - 1) / tb), dim3(tb), 0,
+                       stream, s->vals_out, s->sub_start, s->sub_len, s->sub_order,
+                       sub_total, bases.points, s->partials2);
+    HIP_CHECK(hipGetLastError());
+    {
+        // order heads by sub count desc: the handful of long-merge heads
+        // (top-window buckets) otherwise serialize whole waves
+        rocprim::counting_iterator<uint32_t> cit(0);
+        rocprim::radix_sort_pairs_desc(s->sort_temp, s->sort_temp_bytes, s->nsub,
+                                       s->nsub_sorted, cit, s->head_order, hc, 0, 16,
+                                       stream);
+    }
+    hipLaunchKernelGGL(k_msm_seg_merge, dim3((hc + tb - 1) / tb), dim3(tb), 0, stream,
+                       s->keys_out, s->heads, s->sub_off, s->nsub, s->head_order, hc,
+                       s->partials2, s->buckets, c, sh.key_shift);
+    HIP_CHECK(hipGetLastError());
+    et.mark(stream);
+    return RNG_OK;
+}
+
+// Stage 2: per-chunk suffix sums of s->buckets, then the per-(group,
+// sub-block) combine.  Leaves G*subb Jacobians in s->window_sums.
+static int msm_window_sums(const MsmShape& sh, MsmScratch* s, EvtTimer& et,
+                           hipStream_t stream) {
+    const uint32_t tb = 256;
+    hipLaunchKernelGGL(k_msm_window_chunks, dim3((uint32_t)((sh.nchunks + tb - 1) / tb)),
+                       dim3(tb), 0, stream, s->buckets, sh.c, sh.G, sh.chunk_sz,
+                       s->partials);
+    HIP_CHECK(hipGetLastError());
+    et.mark(stream);
+    const bool scan2 = sh.cw % sh.subb == 0 && (sh.cw / sh.subb) % 64 == 0;
+    if (msm_env().debug)
+        fprintf(stderr, "[msm] n=%lu B=%u c=%u chunk=%u cw=%u subb=%u combine=%s\n",
+                (unsigned long)sh.n, sh.B, sh.c, sh.chunk_sz, sh.cw, sh.subb,
+                scan2 ? "scan2" : "v1");
+    if (scan2)  // scan-based combine: no per-chunk scalar weights
+        hipLaunchKernelGGL(k_msm_window_combine2, dim3(sh.G * sh.subb), dim3(64), 0, stream,
+                           s->partials, sh.c, sh.chunk_sz, sh.subb, s->window_sums);
+    else
+        hipLaunchKernelGGL(k_msm_window_combine, dim3(sh.G * sh.subb), dim3(64), 0, stream,
+                           s->partials, sh.c, sh.chunk_sz, sh.subb, s->window_sums);
+    HIP_CHECK(hipGetLastError());
+    et.mark(stream);
+    return RNG_OK;
+}
+
+// Stage 3, on the host (a single-lane dependent EC chain is far faster on a
+// host core than on one GPU lane).  Two pooled steps: per-(poly, window)
+// sub-block reduction, then the per-poly Horner across windows (the window
+// count is small; a serial 1024-add fold on one core showed up at B=1 with
+// wide subb).
+static void msm_host_fold(const MsmShape& sh, const std::vector<G1Jac>& wsums,
+                          G1Jac* h_result) {
+    const uint32_t G = sh.G, W = sh.W, subb = sh.subb, c = sh.c;
     std::vector<G1Jac> wred((size_t)G);
     auto red_one = [&](uint32_t g) {
         G1Jac sum = wsums[(size_t)g * subb];
@@ -854,23 +741,40 @@ static int msm_dev_run(const G1Aff* d_bases, const uint64_t* d_scalars, uint64_t
         HostPool::inst().parallel_for(G, red_one);
     else
         for (uint32_t g = 0; g < G; ++g) red_one(g);
-    if (B >= 8)
-        HostPool::inst().parallel_for(B, fold_one);
+    if (sh.B >= 8)
+        HostPool::inst().parallel_for(sh.B, fold_one);
     else
-        for (uint32_t b = 0; b < B; ++b) fold_one(b);
+        for (uint32_t b = 0; b < sh.B; ++b) fold_one(b);
+}
+
+// B polynomials of n canonical scalars each (device) against one base
+// description -> one fused pipeline; h_result[B].
+static int msm_dev_run(const MsmBases& bases, const uint64_t* d_scalars, uint64_t n,
+                       uint32_t c, G1Jac* h_result, uint32_t B = 1,
+                       hipStream_t stream = RNG_STREAM) {
+    const MsmShape sh = msm_shape(n, B, c, bases.fixed());
+    MsmScratch* s = nullptr;
+    int rc = msm_scratch_ensure(sh, stream, &s);
+    if (rc != RNG_OK) return rc;
+    // six marks -> tls_msm_times: digits, sort (to the reduce launch),
+    // bucket_reduce (+ merge), window_chunks, final (combine)
+    EvtTimer et;
+    et.mark(stream);
+    if ((rc = msm_bucket_sums(sh, bases, d_scalars, s, et, stream)) != RNG_OK) return rc;
+    if ((rc = msm_window_sums(sh, s, et, stream)) != RNG_OK) return rc;
+    std::vector<G1Jac> wsums((size_t)sh.G * sh.subb);
+    HIP_CHECK(hipMemcpyAsync(wsums.data(), s->window_sums,
+                             sh.G * sh.subb * sizeof(G1Jac), hipMemcpyDeviceToHost,
+                             stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    et.collect(tls_msm_times, 5);
+    msm_host_fold(sh, wsums, h_result);
     return RNG_OK;
 }
 
 // ---- fixed-base MSM over the SRS ----
-// RNG_MSM_FIXED=0 restores the windowed (variable-base) path for A/B runs;
-// the GLV and binned A/B knobs also stay on the windowed path.
-static inline bool msm_fixed_enabled() {
-    static int v = [] {
-        const char* e = getenv("RNG_MSM_FIXED");
-        return e ? atoi(e) : 1;
-    }();
-    return v != 0 && !msm_glv_enabled() && !msm_binned_enabled();
-}
+// RNG_MSM_FIXED=0 restores the windowed (variable-base) path for A/B runs
+static inline bool msm_fixed_enabled() { return msm_env().fixed != 0; }
 
 // Window table for window size c, built on first use.  Returns nullptr when
 // no table is allowed (over 1 GiB, index past 31 bits, all three slots taken
@@ -912,10 +816,7 @@ static const G1Aff* msm_fixed_table(RngCtxImpl* ctx, uint32_t c) {
 static int msm_srs_run(RngCtxImpl* ctx, const uint64_t* d_canon, uint64_t m, uint32_t B,
                        G1Jac* res, int window_c = 0, int mode = 0) {
     if (m == 0 || m > ctx->srs_count || B == 0) return RNG_ERR_BAD_ARG;
-    static int c_env = [] {
-        const char* e = getenv("RNG_MSM_C");
-        return e ? atoi(e) : 0;
-    }();
+    const int c_env = msm_env().c;
     if (window_c == 0 && c_env >= 8 && c_env <= 16) window_c = c_env;
     if (window_c != 0 && (window_c < 8 || window_c > 16)) return RNG_ERR_BAD_ARG;
     if (mode == 1 || (mode == 0 && msm_fixed_enabled())) {
@@ -924,14 +825,13 @@ static int msm_srs_run(RngCtxImpl* ctx, const uint64_t* d_canon, uint64_t m, uin
         while ((1u << gb) <= B) ++gb;
         const G1Aff* table = (c + gb <= 32) ? msm_fixed_table(ctx, c) : nullptr;
         if (table)
-            return msm_dev_run((const G1Aff*)ctx->srs_dev, d_canon, m, c, res, B,
-                               RNG_STREAM, nullptr, table, ctx->srs_count);
+            return msm_dev_run(MsmBases::table(table, ctx->srs_count), d_canon, m, c, res,
+                               B);
         if (mode == 1) return RNG_ERR_BAD_ARG;
     }
     uint32_t c = window_c ? (uint32_t)window_c : msm_auto_c(m);
     if ((uint64_t)B * ((256 + c - 1) / c) > 60000) return RNG_ERR_BAD_ARG;  // g<<16 cap
-    return msm_dev_run((const G1Aff*)ctx->srs_dev, d_canon, m, c, res, B, RNG_STREAM,
-                       (const G1Aff*)ctx->srs_glv_dev);
+    return msm_dev_run(MsmBases::plain((const G1Aff*)ctx->srs_dev), d_canon, m, c, res, B);
 }
 
 // Jacobian (host) -> 9-u64 affine record, using host-side field ops.
@@ -2054,13 +1954,6 @@ RngCtx* rng_prover_init(const uint8_t* srs_ptau, size_t len, uint64_t max_degree
         if (hipMemcpy(im->srs_dev, im->srs_g1_host.data(), npoints * 64,
                       hipMemcpyHostToDevice) != hipSuccess)
             return nullptr;
-        // GLV: precompute the interleaved [P, phi(P)] array once (32 MB at 2^17)
-        if (hipMalloc(&im->srs_glv_dev, npoints * 128) != hipSuccess) return nullptr;
-        uint32_t blocks = (uint32_t)((npoints + 255) / 256);
-        hipLaunchKernelGGL(k_bases_interleave, dim3(blocks), dim3(256), 0, 0,
-                           (const G1Aff*)im->srs_dev, (G1Aff*)im->srs_glv_dev,
-                           (uint32_t)npoints);
-        if (hipDeviceSynchronize() != hipSuccess) return nullptr;
     }
     return ctx.release();
 }
@@ -2319,7 +2212,8 @@ int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,
     uint32_t c = window_c > 0 ? (uint32_t)window_c : msm_auto_c(n);
     if (c < 8 || c > 16) return RNG_ERR_BAD_ARG;
     G1Jac res;
-    int rc = msm_dev_run((const G1Aff*)dev_bases, (const uint64_t*)dev_scalars, n, c, &res, 1);
+    int rc = msm_dev_run(MsmBases::plain((const G1Aff*)dev_bases),
+                         (const uint64_t*)dev_scalars, n, c, &res);
     if (rc != RNG_OK) return rc;
     jac_to_affine_record(res, out9);
     return RNG_OK;
@@ -2783,51 +2677,6 @@ int rng_jj_elgamal(const uint64_t* pk8, const uint64_t* k4, const uint64_t* msg1
     memcpy(out_eph8, ct.ephemeral_key.x.l, 32);
     memcpy(out_eph8 + 4, ct.ephemeral_key.y.l, 32);
     memcpy(out_c12, ct.ciphertext, 96);
-    return RNG_OK;
-}
-
-// GLV decomposition test shim (host mirror of k_glv_decompose's math):
-// canonical scalar -> (|k1|, sign1, |k2|, sign2); tests pin it against the
-// Python derivation in scripts/gen_glv_params.py
-int rng_glv_decompose(const uint64_t* canon4, uint64_t* out_k1, uint64_t* out_sign1,
-                      uint64_t* out_k2, uint64_t* out_sign2) {
-    // reuse the device function's logic via a 1-element host-side emulation:
-    // the kernel math is plain integer C++, so call it through a tiny lambda
-    // duplicating the steps (kept in sync with k_glv_decompose).
-    const u64 G1C[4] = GLV_G1;
-    const u64 G2C[4] = GLV_G2;
-    const u64 A1[2] = GLV_A1;
-    const u64 B1[2] = GLV_B1;
-    const u64 A2[2] = GLV_A2;
-    const u64 B2[2] = GLV_B2;
-    u64 k[4];
-    memcpy(k, canon4, 32);
-    u64 c1[2], c2[2];
-    glv_mul_shift(G1C, k, c1);
-    glv_mul_shift(G2C, k, c2);
-    u64 s1[4], s2[4], S[4], k1[4];
-    glv_mul128(c1, A1, s1);
-    glv_mul128(c2, A2, s2);
-    glv_add4(s1, s2, S);
-    if (glv_cmp4(k, S) >= 0) {
-        glv_sub4(k, S, k1);
-        *out_sign1 = 0;
-    } else {
-        glv_sub4(S, k, k1);
-        *out_sign1 = 1;
-    }
-    u64 t1[4], t2[4], k2[4];
-    glv_mul128(c1, B1, t1);
-    glv_mul128(c2, B2, t2);
-    if (glv_cmp4(t1, t2) >= 0) {
-        glv_sub4(t1, t2, k2);
-        *out_sign2 = 0;
-    } else {
-        glv_sub4(t2, t1, k2);
-        *out_sign2 = 1;
-    }
-    memcpy(out_k1, k1, 32);
-    memcpy(out_k2, k2, 32);
     return RNG_OK;
 }
 

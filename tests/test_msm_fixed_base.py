@@ -188,3 +188,46 @@ def test_mode_auto_equals_fixed(ctx, orc, srs10, B):
     auto = ctx.msm_srs_batch(flat, n, B, mode=AUTO)
     assert np.array_equal(auto, fixed)
     assert np.array_equal(fixed, oracle(orc, g1, flat, n, B))
+
+
+def test_windowed_many_groups_grows_window_sums(ctx, orc, srs10):
+    """Windowed mode at c=8, n=8, B=260: G = 260*32 = 8320 key groups,
+    chunk 8, 16 chunks per window, one sub-block per window.  G*subb passes
+    the 8192 entries window_sums starts with, so the scratch grows, and 16
+    chunks per block is no multiple of 64, so k_msm_window_combine (not
+    combine2) folds them.  A smaller call afterwards reuses the grown
+    scratch."""
+    _, g1 = srs10
+    n, B, c = 8, 260, 8
+    assert B * n_windows(c) > 8192
+    rng = random.Random(8320)
+    polys = [rand_poly(rng, n) for _ in range(B)]
+    polys[1] = [0] * n
+    polys[3] = polys[3][:n // 2] + [0] * (n - n // 2)
+    flat = pack(polys, n)
+    expect = oracle(orc, g1, flat, n, B)
+    assert np.array_equal(expect[1], IDENTITY)
+    got = ctx.msm_srs_batch(flat, n, B, window_c=c, mode=WINDOWED)
+    bad = [b for b in range(B) if not np.array_equal(got[b], expect[b])]
+    assert not bad, f"records {bad} differ from the oracle"
+    small = ctx.msm_srs_batch(flat[:4 * n * 5], n, 5, window_c=c, mode=WINDOWED)
+    assert np.array_equal(small, expect[:5])
+
+
+def test_table_slots_exhausted(ctx, orc, srs10):
+    """A context holds three window tables.  Once c = 8, 10 and 13 own them,
+    a fourth window size gets none: fixed-base mode is an error, auto mode
+    falls back to the windowed path."""
+    from renegade_amd.prover import ProverError
+    _, g1 = srs10
+    rng = random.Random(909)
+    tiny = pack([rand_poly(rng, 4)], 4)
+    for c in FIXED_CS:
+        got = ctx.msm_srs_batch(tiny, 4, 1, window_c=c, mode=FIXED)
+        assert np.array_equal(got, oracle(orc, g1, tiny, 4, 1))
+    n, B = 96, 3
+    flat = pack([rand_poly(rng, n) for _ in range(B)], n)
+    with pytest.raises(ProverError, match="rc=-2"):  # RNG_ERR_BAD_ARG
+        ctx.msm_srs_batch(flat, n, B, window_c=9, mode=FIXED)
+    got = ctx.msm_srs_batch(flat, n, B, window_c=9, mode=AUTO)
+    assert np.array_equal(got, oracle(orc, g1, flat, n, B))
