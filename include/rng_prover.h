@@ -127,6 +127,22 @@ int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,
 int rng_msm_srs_batch(RngCtx* ctx, const uint64_t* scalars, uint64_t n, uint32_t B,
                       int window_c, int mode, uint64_t* out9xB);
 
+/* PlonK permutation grand product z(X) on the GPU (round 2 of the prover).
+ * For proof p and row t, with w the n-th root of unity and k_j = k5[j]:
+ *   num_p(t) = prod_{j<5} ( w_p[j][t] + beta_p * k_j * w^t     + gamma_p )
+ *   den_p(t) = prod_{j<5} ( w_p[j][t] + beta_p * sigma[j][t]   + gamma_p )
+ *   z_p[0] = 1,   z_p[i] = prod_{t<i} num_p(t) / den_p(t)      (1 <= i < n)
+ * computed as z_i = P_{i-1} * S_i * Q^-1 (P prefix products of num, S suffix
+ * products of den, Q = S_0): two batched scans and one inversion per proof.
+ * A zero den(t) gives z_p[0] = 1 and z_p[i] = 0 for i >= 1 (the inverse of
+ * 0 is 0), as the host batch inversion does.
+ * host buffers, Montgomery Fr; wires = batch x 5 x n (column-major per proof),
+ * sigma_evals = 5 x n (shared by the batch), k5 = 5 Fr, beta_gamma = batch x 2 Fr,
+ * out_z = batch x n Fr.  n a power of two, 2 <= n <= 2^17, 1 <= batch <= 128. */
+int rng_perm_product(RngCtx* ctx, const uint64_t* wires, const uint64_t* sigma_evals,
+                     const uint64_t* k5, const uint64_t* beta_gamma,
+                     uint64_t n, uint64_t batch, uint64_t* out_z);
+
 /* Device buffer helpers */
 void* rng_dbuf_alloc(size_t bytes);
 void rng_dbuf_free(void* dbuf);
@@ -177,6 +193,15 @@ int rng_prove_cohort(RngCtx* ctx, const RngProvingKey* pk, uint64_t k,
                      const uint64_t* wires, const uint64_t* public_inputs,
                      const uint64_t* seeds, uint64_t* out_proofs,
                      uint64_t* out_link_hints);
+
+/* Test hook in the style of rng_msm_srs_batch: the SAME internal call the
+ * provers' round 2 makes, against the key's own sigma/omega tables (wires,
+ * beta_gamma and out_z as in rng_perm_product, n = the key's domain size).
+ * mode 0 = what the prover would pick (RNG_Z_DEVICE, else the per-path
+ * default; batch 1 is the single-proof path), 1 = device, 2 = host loop. */
+int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wires,
+                        const uint64_t* beta_gamma, uint64_t batch, int mode,
+                        uint64_t* out_z);
 
 int rng_verify(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* public_inputs,
                const uint64_t* proof);

@@ -23,6 +23,7 @@
 #include "ntt_kernels.hip"
 #include "msm_kernels.hip"
 #include "plonk_kernels.hip"
+#include "perm_kernels.hip"
 #include "plonk_circuit.hpp"
 #include "plonk_host.hpp"
 #include "test_circuits.hpp"
@@ -922,9 +923,12 @@ struct PlonkPkImpl {
     Fr* sel_coset = nullptr;   // device 13*m
     Fr* sig_coset = nullptr;   // device 5*m
     Fr* l1_coset = nullptr;    // device m
+    Fr* sig_evals_dev = nullptr;  // device 5*n (grand-product stage)
+    Fr* wpow_dev = nullptr;       // device n: w^t
     RngCtxImpl* ctx = nullptr;
     ~PlonkPkImpl() {
-        for (void* b : {(void*)sel_coset, (void*)sig_coset, (void*)l1_coset})
+        for (void* b : {(void*)sel_coset, (void*)sig_coset, (void*)l1_coset,
+                        (void*)sig_evals_dev, (void*)wpow_dev})
             hip_free_guarded(b);
     }
 };
@@ -945,6 +949,141 @@ static int prove_scratch_ensure(uint64_t n) {
     HIP_CHECK(hipMalloc(&s->canon, 13 * 4 * (n + 3) * 8));
     s->n = n;
     s->m = m;
+    return RNG_OK;
+}
+
+// ---------------- R2: permutation grand product ----------------
+
+// RNG_Z_DEVICE, read once per process: 0 = host loops, 1 = device stage
+// (perm_kernels.hip) in both provers.  Unset: per-path defaults below, set
+// by the A/B measurement in DESIGN.md §4.5.
+constexpr bool Z_DEVICE_DEFAULT_SINGLE = true;
+constexpr bool Z_DEVICE_DEFAULT_COHORT = true;
+static int z_device_env() {
+    static const int v = [] {
+        const char* e = getenv("RNG_Z_DEVICE");
+        return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+    }();
+    return v;
+}
+static bool z_device_single() {
+    return z_device_env() < 0 ? Z_DEVICE_DEFAULT_SINGLE : z_device_env() == 1;
+}
+static bool z_device_cohort() {
+    return z_device_env() < 0 ? Z_DEVICE_DEFAULT_COHORT : z_device_env() == 1;
+}
+
+// host loop: n evaluations of one proof's z into ze
+static void perm_product_host(const PlonkPkImpl& pk, const Fr& w, const Fr* wires,
+                              const Fr& beta, const Fr& gamma, Fr* ze) {
+    const uint64_t n = pk.n;
+    std::vector<Fr> znum(n), zden(n);
+    Fr wi = Fr::one();
+    for (uint64_t i = 0; i < n; ++i) {
+        Fr num = Fr::one(), den = Fr::one();
+        for (int j = 0; j < 5; ++j) {
+            Fr wv = wires[(size_t)j * n + i];
+            num = num.mul(wv.add(beta.mul(pk.k[j]).mul(wi)).add(gamma));
+            den = den.mul(wv.add(beta.mul(pk.sig_evals[j][i])).add(gamma));
+        }
+        znum[i] = num;
+        zden[i] = den;
+        wi = wi.mul(w);
+    }
+    std::vector<Fr> zden_inv = hbatch_inverse(zden);
+    ze[0] = Fr::one();
+    for (uint64_t i = 1; i < n; ++i) ze[i] = ze[i - 1].mul(znum[i - 1]).mul(zden_inv[i - 1]);
+}
+
+struct PermScratch {  // per-thread small buffers of the device stage (~2 MiB)
+    Fr* dev = nullptr;       // one allocation, carved below
+    Fr* tile_tot = nullptr;  // 2*PERM_MAX_BATCH * PERM_MAX_TILES
+    Fr* tile_pre = nullptr;  // same
+    Fr* totals = nullptr;    // 2*PERM_MAX_BATCH sequence totals (num, then den)
+    Fr* qinv = nullptr;      // PERM_MAX_BATCH
+    Fr* bg = nullptr;        // PERM_MAX_BATCH x (beta, gamma)
+    std::vector<Fr> h_bg, h_q;  // host staging (outlives the async copies)
+    ~PermScratch() { hip_free_guarded(dev); }
+};
+
+static thread_local std::unique_ptr<PermScratch> tls_perm_scratch;
+
+static PermScratch* perm_scratch_get() {
+    if (tls_perm_scratch) return tls_perm_scratch.get();
+    auto s = std::make_unique<PermScratch>();
+    const size_t tiles = (size_t)2 * PERM_MAX_BATCH * PERM_MAX_TILES;
+    const size_t elems = 2 * tiles + 5 * (size_t)PERM_MAX_BATCH;
+    if (hipMalloc(&s->dev, elems * sizeof(Fr)) != hipSuccess) return nullptr;
+    s->tile_tot = s->dev;
+    s->tile_pre = s->tile_tot + tiles;
+    s->totals = s->tile_pre + tiles;
+    s->qinv = s->totals + 2 * PERM_MAX_BATCH;
+    s->bg = s->qinv + PERM_MAX_BATCH;
+    s->h_bg.resize(2 * PERM_MAX_BATCH);
+    s->h_q.resize(PERM_MAX_BATCH);
+    tls_perm_scratch = std::move(s);
+    return tls_perm_scratch.get();
+}
+
+// The device stage, on RNG_STREAM.  Device pointers: wires (batch x 5 x n),
+// sigma (5 x n), wpow (n), nd (2*batch*n workspace: num/den terms, scanned in
+// place), z (batch x n out; may not alias nd).  bg = batch x (beta, gamma) on
+// the host.  One stream sync in the middle: the batch den totals come back,
+// are inverted on the host (a Fermat chain is a ~380-deep dependent
+// multiplication chain, tens of µs on a host core against an estimated
+// millisecond on one GPU lane) and go up again.
+static int perm_product_dev(const Fr* wires, const Fr* sigma, const Fr* wpow,
+                            const Fr k5[5], const Fr* bg, uint64_t n64, uint64_t batch64,
+                            Fr* nd, Fr* z) {
+    if (n64 < 2 || (n64 & (n64 - 1)) || n64 > PERM_MAX_N || batch64 < 1 ||
+        batch64 > PERM_MAX_BATCH)
+        return RNG_ERR_BAD_ARG;
+    const uint32_t n = (uint32_t)n64, batch = (uint32_t)batch64;
+    PermScratch* ps = perm_scratch_get();
+    if (!ps) return RNG_ERR_HIP;
+    memcpy(ps->h_bg.data(), bg, 2 * (size_t)batch * sizeof(Fr));
+    HIP_CHECK(hipMemcpyAsync(ps->bg, ps->h_bg.data(), 2 * (size_t)batch * sizeof(Fr),
+                             hipMemcpyHostToDevice, RNG_STREAM));
+    PermK5 kk;
+    for (int j = 0; j < 5; ++j) kk.k[j] = k5[j];
+    const uint32_t rows_blocks = (uint32_t)(((uint64_t)batch * n + 255) / 256);
+    hipLaunchKernelGGL(k_perm_terms, dim3(rows_blocks), dim3(256), 0, RNG_STREAM, wires,
+                       sigma, wpow, ps->bg, kk, nd, n, batch);
+    HIP_CHECK(hipGetLastError());
+    const uint32_t tiles = (n + PERM_TILE - 1) / PERM_TILE, nseq = 2 * batch;
+    if (tiles == 1) {
+        hipLaunchKernelGGL(k_perm_scan_apply<false>, dim3(nseq), dim3(PERM_WG), 0,
+                           RNG_STREAM, nd, (const Fr*)nullptr, ps->totals, n, 1u, batch);
+        HIP_CHECK(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(k_perm_tile_reduce, dim3(nseq * tiles), dim3(PERM_WG), 0,
+                           RNG_STREAM, nd, ps->tile_tot, n, tiles, batch);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_perm_tile_prefix, dim3(nseq), dim3(PERM_WG), 0, RNG_STREAM,
+                           ps->tile_tot, ps->tile_pre, ps->totals, tiles);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_perm_scan_apply<true>, dim3(nseq * tiles), dim3(PERM_WG), 0,
+                           RNG_STREAM, nd, ps->tile_pre, ps->totals, n, tiles, batch);
+        HIP_CHECK(hipGetLastError());
+    }
+    // Q^-1 per proof; a zero total inverts to zero (Fermat), and must not
+    // zero the other proofs' inverses in the shared batch inversion
+    HIP_CHECK(hipMemcpyAsync(ps->h_q.data(), ps->totals + batch, batch * sizeof(Fr),
+                             hipMemcpyDeviceToHost, RNG_STREAM));
+    HIP_CHECK(hipStreamSynchronize(RNG_STREAM));
+    {
+        std::vector<Fr> q(ps->h_q.begin(), ps->h_q.begin() + batch);
+        for (auto& v : q)
+            if (v.is_zero()) v = Fr::one();
+        q = hbatch_inverse(q);
+        for (uint32_t p = 0; p < batch; ++p)
+            ps->h_q[p] = ps->h_q[p].is_zero() ? Fr::zero() : q[p];
+    }
+    HIP_CHECK(hipMemcpyAsync(ps->qinv, ps->h_q.data(), batch * sizeof(Fr),
+                             hipMemcpyHostToDevice, RNG_STREAM));
+    hipLaunchKernelGGL(k_perm_finalize, dim3(rows_blocks), dim3(256), 0, RNG_STREAM, nd,
+                       ps->qinv, z, n, batch);
+    HIP_CHECK(hipGetLastError());
     return RNG_OK;
 }
 
@@ -1153,6 +1292,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     CohortScratch* cs = tls_cohort_scratch.get();
     HostPool& pool = HostPool::inst();
     Fr w = h_fr_root_of_unity((uint32_t)n);
+    const bool z_dev = z_device_cohort() && n <= PERM_MAX_N;
 
     std::vector<HostDrbg> drbg;
     drbg.reserve(k);
@@ -1174,8 +1314,20 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     COHORT_TRACE("r1");
     // --- R1: wire polys (one batched IFFT + one fused MSM) ---
     {
-        HIP_CHECK(hipMemcpyAsync(cs->stage, wires_all, (size_t)5 * k * n * sizeof(Fr),
-                                 hipMemcpyHostToDevice, RNG_STREAM));
+        if (z_dev) {
+            // the IFFT and the blinding below overwrite stage, and R2's device
+            // grand product needs the evaluations again: upload into
+            // coset_out (unused until R3, so no extra memory) and stage a copy
+            HIP_CHECK(hipMemcpyAsync(cs->coset_out, wires_all,
+                                     (size_t)5 * k * n * sizeof(Fr),
+                                     hipMemcpyHostToDevice, RNG_STREAM));
+            HIP_CHECK(hipMemcpyAsync(cs->stage, cs->coset_out,
+                                     (size_t)5 * k * n * sizeof(Fr),
+                                     hipMemcpyDeviceToDevice, RNG_STREAM));
+        } else {
+            HIP_CHECK(hipMemcpyAsync(cs->stage, wires_all, (size_t)5 * k * n * sizeof(Fr),
+                                     hipMemcpyHostToDevice, RNG_STREAM));
+        }
         COHORT_TRACE("r1-ifft");
         int rc = ntt_dev_run(ctx, cs->stage, cs->ntt_tmp, (uint32_t)n, 5 * (uint64_t)k,
                              true, RNG_STREAM);
@@ -1236,37 +1388,40 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     }
 
     COHORT_TRACE("r2");
-    // --- R2: grand products (host pool) + batched IFFT of z and PI ---
+    // --- R2: grand products (device stage or host pool) + batched IFFT of
+    //     z and PI ---
     {
-        std::vector<Fr> evals_flat(2 * (size_t)k * n);  // k z-cols + k PI-cols
+        // stage = k z-cols then k PI-cols; the device stage writes the z half
+        // in place (terms and scans in q_all, free until R3), so only the
+        // PI half is uploaded
+        std::vector<Fr> evals_flat((z_dev ? 1 : 2) * (size_t)k * n);
+        Fr* pi_base = evals_flat.data() + (z_dev ? 0 : (size_t)k * n);
         pool.parallel_for(k, [&](uint32_t p) {
-            const Fr* wires = wires_all + (size_t)5 * p * n;
-            std::vector<Fr> znum(n), zden(n);
-            Fr wi = Fr::one();
-            for (uint64_t i = 0; i < n; ++i) {
-                Fr num = Fr::one(), den = Fr::one();
-                for (int j = 0; j < 5; ++j) {
-                    Fr wv = wires[(size_t)j * n + i];
-                    num = num.mul(wv.add(beta[p].mul(pk.k[j]).mul(wi)).add(gamma[p]));
-                    den = den.mul(wv.add(beta[p].mul(pk.sig_evals[j][i])).add(gamma[p]));
-                }
-                znum[i] = num;
-                zden[i] = den;
-                wi = wi.mul(w);
-            }
-            std::vector<Fr> zden_inv = hbatch_inverse(zden);
-            Fr* ze = evals_flat.data() + (size_t)p * n;
-            ze[0] = Fr::one();
-            for (uint64_t i = 1; i < n; ++i)
-                ze[i] = ze[i - 1].mul(znum[i - 1]).mul(zden_inv[i - 1]);
-            Fr* pie = evals_flat.data() + ((size_t)k + p) * n;
+            if (!z_dev)
+                perm_product_host(pk, w, wires_all + (size_t)5 * p * n, beta[p], gamma[p],
+                                  evals_flat.data() + (size_t)p * n);
+            Fr* pie = pi_base + (size_t)p * n;
             for (uint64_t i = 0; i < n; ++i) pie[i] = Fr::zero();
             const Fr* pubs = pubs_all + (size_t)p * pk.npub;
             for (uint64_t i = 0; i < pk.npub; ++i) pie[i] = pubs[i];
         });
-        HIP_CHECK(hipMemcpyAsync(cs->stage, evals_flat.data(),
-                                 2 * (size_t)k * n * sizeof(Fr), hipMemcpyHostToDevice,
-                                 RNG_STREAM));
+        if (z_dev) {
+            std::vector<Fr> bg(2 * (size_t)k);
+            for (uint32_t p = 0; p < k; ++p) {
+                bg[2 * (size_t)p] = beta[p];
+                bg[2 * (size_t)p + 1] = gamma[p];
+            }
+            int prc = perm_product_dev(cs->coset_out, pk.sig_evals_dev, pk.wpow_dev, pk.k,
+                                       bg.data(), n, k, cs->q_all, cs->stage);
+            if (prc != RNG_OK) return prc;
+            HIP_CHECK(hipMemcpyAsync(cs->stage + (size_t)k * n, evals_flat.data(),
+                                     (size_t)k * n * sizeof(Fr), hipMemcpyHostToDevice,
+                                     RNG_STREAM));
+        } else {
+            HIP_CHECK(hipMemcpyAsync(cs->stage, evals_flat.data(),
+                                     2 * (size_t)k * n * sizeof(Fr),
+                                     hipMemcpyHostToDevice, RNG_STREAM));
+        }
         int rc = ntt_dev_run(ctx, cs->stage, cs->ntt_tmp, (uint32_t)n, 2 * (uint64_t)k,
                              true, RNG_STREAM);
         if (rc != RNG_OK) return rc;
@@ -1548,6 +1703,21 @@ static int ifft_columns(RngCtxImpl* ctx, const Fr* host_evals, uint64_t n,
     return rc;
 }
 
+// same for evals ALREADY on the device: d_in (n*ncols, clobbered) through
+// the inverse NTT into d_out (n*ncols), columns downloaded to the host
+static int ifft_columns_dev(RngCtxImpl* ctx, Fr* d_in, Fr* d_out, uint64_t n,
+                            uint64_t ncols, std::vector<Fr>* out_cols) {
+    int rc = ntt_dev_run(ctx, d_in, d_out, (uint32_t)n, ncols, true, RNG_STREAM);
+    if (rc != RNG_OK) return rc;
+    for (uint64_t c = 0; c < ncols; ++c) {
+        out_cols[c].resize(n);
+        HIP_CHECK(hipMemcpyAsync(out_cols[c].data(), d_out + c * n, n * sizeof(Fr),
+                                 hipMemcpyDeviceToHost, RNG_STREAM));
+    }
+    HIP_CHECK(hipStreamSynchronize(RNG_STREAM));
+    return RNG_OK;
+}
+
 static int plonk_preprocess_impl(RngCtxImpl* ctx, const RngCircuitDesc* d,
                                  PlonkPkImpl* pk) {
     const uint64_t n = d->n, m = 8 * n;
@@ -1576,6 +1746,12 @@ static int plonk_preprocess_impl(RngCtxImpl* ctx, const RngCircuitDesc* d,
     }
     if (ifft_columns(ctx, sig_evals_flat.data(), n, 5, pk->sigp) != RNG_OK)
         return RNG_ERR_HIP;
+    // device tables of the grand-product stage (6n Fr per key)
+    HIP_CHECK(hipMalloc(&pk->sig_evals_dev, 5 * n * sizeof(Fr)));
+    HIP_CHECK(hipMalloc(&pk->wpow_dev, n * sizeof(Fr)));
+    HIP_CHECK(hipMemcpy(pk->sig_evals_dev, sig_evals_flat.data(), 5 * n * sizeof(Fr),
+                        hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(pk->wpow_dev, wpow.data(), n * sizeof(Fr), hipMemcpyHostToDevice));
 
     // commitments (two fused batch MSMs)
     {
@@ -1639,7 +1815,20 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
 
     // --- R1: wire polys ---
     std::vector<Fr> wpoly[5];
-    if (ifft_columns(ctx, wires, n, 5, wpoly) != RNG_OK) return RNG_ERR_HIP;
+    const bool z_dev = z_device_single() && n <= PERM_MAX_N;
+    if (z_dev) {
+        // the wire evaluations go up once and stay in w_coset (free until
+        // R3) for the device grand product; the IFFT runs on a copy
+        Fr* wev = sc->w_coset;
+        HIP_CHECK(hipMemcpyAsync(wev, wires, 5 * n * sizeof(Fr), hipMemcpyHostToDevice,
+                                 RNG_STREAM));
+        HIP_CHECK(hipMemcpyAsync(sc->q_buf, wev, 5 * n * sizeof(Fr),
+                                 hipMemcpyDeviceToDevice, RNG_STREAM));
+        if (ifft_columns_dev(ctx, sc->q_buf, sc->tmp, n, 5, wpoly) != RNG_OK)
+            return RNG_ERR_HIP;
+    } else if (ifft_columns(ctx, wires, n, 5, wpoly) != RNG_OK) {
+        return RNG_ERR_HIP;
+    }
     for (int j = 0; j < 5; ++j) {
         Fr b0 = drbg.next(), b1 = drbg.next();
         wpoly[j].resize(n + 2, Fr::zero());
@@ -1666,28 +1855,21 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
     Fr gamma = tr.challenge();
 
     // --- R2: grand product ---
-    std::vector<Fr> znum(n), zden(n);
-    {
-        Fr wi = Fr::one();
-        for (uint64_t i = 0; i < n; ++i) {
-            Fr num = Fr::one(), den = Fr::one();
-            for (int j = 0; j < 5; ++j) {
-                Fr wv = wires[(size_t)j * n + i];
-                num = num.mul(wv.add(beta.mul(pk.k[j]).mul(wi)).add(gamma));
-                den = den.mul(wv.add(beta.mul(pk.sig_evals[j][i])).add(gamma));
-            }
-            znum[i] = num;
-            zden[i] = den;
-            wi = wi.mul(w);
-        }
-    }
-    std::vector<Fr> zden_inv = hbatch_inverse(zden);
-    std::vector<Fr> zevals(n);
-    zevals[0] = Fr::one();
-    for (uint64_t i = 1; i < n; ++i)
-        zevals[i] = zevals[i - 1].mul(znum[i - 1]).mul(zden_inv[i - 1]);
     std::vector<Fr> zpoly[1];
-    if (ifft_columns(ctx, zevals.data(), n, 1, zpoly) != RNG_OK) return RNG_ERR_HIP;
+    if (z_dev) {
+        // device stage: terms/scans in q_buf, z evaluations in z_coset, and
+        // straight into the inverse NTT; only the n coefficients come back
+        const Fr bg[2] = {beta, gamma};
+        int rc = perm_product_dev(sc->w_coset, pk.sig_evals_dev, pk.wpow_dev, pk.k, bg, n,
+                                  1, sc->q_buf, sc->z_coset);
+        if (rc != RNG_OK) return rc;
+        if (ifft_columns_dev(ctx, sc->z_coset, sc->tmp, n, 1, zpoly) != RNG_OK)
+            return RNG_ERR_HIP;
+    } else {
+        std::vector<Fr> zevals(n);
+        perm_product_host(pk, w, wires, beta, gamma, zevals.data());
+        if (ifft_columns(ctx, zevals.data(), n, 1, zpoly) != RNG_OK) return RNG_ERR_HIP;
+    }
     {
         Fr b2 = drbg.next(), b3 = drbg.next(), b4 = drbg.next();
         zpoly[0].resize(n + 3, Fr::zero());
@@ -4057,6 +4239,80 @@ int rng_prove_cohort(RngCtx* ctx, const RngProvingKey* pk, uint64_t k,
     return plonk_prove_cohort_impl(&ctx->impl, pk->impl, (uint32_t)k,
                                    (const Fr*)wires, (const Fr*)public_inputs, seeds,
                                    out_proofs, out_link_hints);
+}
+
+// host wires (batch x 5 x n) + device tables -> host z (batch x n) through
+// perm_product_dev, the provers' own R2 call
+static int perm_product_hosted(const uint64_t* wires, const Fr* d_sigma, const Fr* d_wpow,
+                               const Fr k5[5], const uint64_t* beta_gamma, uint64_t n,
+                               uint64_t batch, uint64_t* out_z) {
+    const size_t rows = (size_t)batch * n;
+    Fr* d = nullptr;  // wires (5 rows) | num/den workspace (2 rows) | z (rows)
+    HIP_CHECK(hipMalloc(&d, 8 * rows * sizeof(Fr)));
+    int rc = RNG_OK;
+    if (hipMemcpyAsync(d, wires, 5 * rows * sizeof(Fr), hipMemcpyHostToDevice,
+                       RNG_STREAM) != hipSuccess)
+        rc = RNG_ERR_HIP;
+    if (rc == RNG_OK)
+        rc = perm_product_dev(d, d_sigma, d_wpow, k5, (const Fr*)beta_gamma, n, batch,
+                              d + 5 * rows, d + 7 * rows);
+    if (rc == RNG_OK &&
+        (hipMemcpyAsync(out_z, d + 7 * rows, rows * sizeof(Fr), hipMemcpyDeviceToHost,
+                        RNG_STREAM) != hipSuccess ||
+         hipStreamSynchronize(RNG_STREAM) != hipSuccess))
+        rc = RNG_ERR_HIP;
+    hipFree(d);
+    return rc;
+}
+
+int rng_perm_product(RngCtx* ctx, const uint64_t* wires, const uint64_t* sigma_evals,
+                     const uint64_t* k5, const uint64_t* beta_gamma, uint64_t n,
+                     uint64_t batch, uint64_t* out_z) {
+    if (!gpu_ok()) return RNG_ERR_NO_GPU;
+    if (!ctx || !wires || !sigma_evals || !k5 || !beta_gamma || !out_z || n < 2 ||
+        (n & (n - 1)) || n > PERM_MAX_N || batch < 1 || batch > PERM_MAX_BATCH)
+        return RNG_ERR_BAD_ARG;
+    Fr* t = nullptr;  // sigma (5n) | w^t (n)
+    HIP_CHECK(hipMalloc(&t, 6 * n * sizeof(Fr)));
+    int rc = RNG_OK;
+    if (hipMemcpyAsync(t, sigma_evals, 5 * n * sizeof(Fr), hipMemcpyHostToDevice,
+                       RNG_STREAM) != hipSuccess)
+        rc = RNG_ERR_HIP;
+    if (rc == RNG_OK) {
+        hipLaunchKernelGGL(k_pow_table, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0,
+                           RNG_STREAM, t + 5 * n, h_fr_root_of_unity((uint32_t)n),
+                           (uint64_t)1, n);
+        if (hipGetLastError() != hipSuccess) rc = RNG_ERR_HIP;
+    }
+    if (rc == RNG_OK)
+        rc = perm_product_hosted(wires, t, t + 5 * n, (const Fr*)k5, beta_gamma, n, batch,
+                                 out_z);
+    hipFree(t);
+    return rc;
+}
+
+int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wires,
+                        const uint64_t* beta_gamma, uint64_t batch, int mode,
+                        uint64_t* out_z) {
+    if (!gpu_ok()) return RNG_ERR_NO_GPU;
+    if (!ctx || !pk || !wires || !beta_gamma || !out_z || batch < 1 ||
+        batch > PERM_MAX_BATCH || mode < 0 || mode > 2)
+        return RNG_ERR_BAD_ARG;
+    const PlonkPkImpl& impl = pk->impl;
+    const uint64_t n = impl.n;
+    bool dev = mode == 1;
+    if (mode == 0)  // rng_prove_cohort sends k = 1 down the single-proof path
+        dev = (batch == 1 ? z_device_single() : z_device_cohort()) && n <= PERM_MAX_N;
+    if (dev)
+        return perm_product_hosted(wires, impl.sig_evals_dev, impl.wpow_dev, impl.k, beta_gamma, n,
+                                   batch, out_z);
+    const Fr w = h_fr_root_of_unity((uint32_t)n);
+    const Fr* bg = (const Fr*)beta_gamma;
+    HostPool::inst().parallel_for((uint32_t)batch, [&](uint32_t p) {
+        perm_product_host(impl, w, (const Fr*)wires + (size_t)5 * p * n, bg[2 * p],
+                          bg[2 * p + 1], (Fr*)out_z + (size_t)p * n);
+    });
+    return RNG_OK;
 }
 
 // PK introspection for tests / the verifier side

@@ -68,6 +68,11 @@ class ProverLib:
         self.lib.rng_msm_srs_batch.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_uint64,
                                                ctypes.c_uint32, ctypes.c_int,
                                                ctypes.c_int, _U64P]
+        self.lib.rng_perm_product.argtypes = [ctypes.c_void_p, _U64P, _U64P, _U64P, _U64P,
+                                              ctypes.c_uint64, ctypes.c_uint64, _U64P]
+        self.lib.rng_perm_product_pk.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _U64P,
+                                                 _U64P, ctypes.c_uint64, ctypes.c_int,
+                                                 _U64P]
         self.lib.rng_srs_dev_bases.restype = ctypes.c_void_p
         self.lib.rng_srs_dev_bases.argtypes = [ctypes.c_void_p, _U64P]
 
@@ -160,6 +165,38 @@ class ProverCtx:
         self._check(self.lib.rng_msm_srs_batch(self.h, _ptr(scalars), n, batch, window_c,
                                                mode, _ptr(out)), "rng_msm_srs_batch")
         return out.reshape(batch, 9)
+
+    Z_AUTO, Z_DEVICE, Z_HOST = 0, 1, 2
+
+    def perm_product(self, wires: np.ndarray, sigma_evals: np.ndarray, k5: np.ndarray,
+                     beta_gamma: np.ndarray, n: int, batch: int = 1):
+        """Permutation grand product z on the GPU.  Montgomery limbs: wires
+        batch*5*n Fr (column-major per proof), sigma_evals 5*n Fr, k5 5 Fr,
+        beta_gamma batch*(beta, gamma).  Returns a (batch, n, 4) array."""
+        for a, fr in ((wires, 5 * n * batch), (sigma_evals, 5 * n), (k5, 5),
+                      (beta_gamma, 2 * batch)):
+            assert a.dtype == np.uint64 and a.size == 4 * fr
+        args = [np.ascontiguousarray(a).reshape(-1)
+                for a in (wires, sigma_evals, k5, beta_gamma)]
+        out = np.zeros(4 * n * batch, dtype=np.uint64)
+        self._check(self.lib.rng_perm_product(self.h, *map(_ptr, args), n, batch,
+                                              _ptr(out)), "rng_perm_product")
+        return out.reshape(batch, n, 4)
+
+    def perm_product_pk(self, pk, wires: np.ndarray, beta_gamma: np.ndarray, n: int,
+                        batch: int = 1, mode: int = 0):
+        """The provers' own round-2 call against proving key `pk` (a
+        rng_preprocess handle of domain size n).  mode: Z_AUTO / Z_DEVICE /
+        Z_HOST.  Returns a (batch, n, 4) array."""
+        assert wires.dtype == np.uint64 and wires.size == 4 * 5 * n * batch
+        assert beta_gamma.dtype == np.uint64 and beta_gamma.size == 8 * batch
+        wires = np.ascontiguousarray(wires).reshape(-1)
+        beta_gamma = np.ascontiguousarray(beta_gamma).reshape(-1)
+        out = np.zeros(4 * n * batch, dtype=np.uint64)
+        self._check(self.lib.rng_perm_product_pk(self.h, ctypes.c_void_p(pk), _ptr(wires),
+                                                 _ptr(beta_gamma), batch, mode,
+                                                 _ptr(out)), "rng_perm_product_pk")
+        return out.reshape(batch, n, 4)
 
     # ---- device-resident helpers (benchmarking) ----
     def dbuf_from(self, host: np.ndarray):
