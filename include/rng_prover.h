@@ -127,6 +127,21 @@ int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,
 int rng_msm_srs_batch(RngCtx* ctx, const uint64_t* scalars, uint64_t n, uint32_t B,
                       int window_c, int mode, uint64_t* out9xB);
 
+/* Test hook: the provers' round-1 commitment on the Lagrange path (the same
+ * internal call).  B evaluation vectors over the size-n domain (n a power of
+ * two, n + 2 <= SRS points), CANONICAL scalars: evals = B*n*4 u64, blinders
+ * = B*2*4 u64 (b0, b1 per polynomial) or NULL.  Commits
+ * sum_i evals[i]*[L_i(tau)] + b0*([tau^n] - [tau^0]) + b1*([tau^(n+1)] - [tau^1]),
+ * which equals the SRS commitment of the blinded coefficient form.
+ * window_c in [8,16], 0 = the prover's own rule for a sparse batch (a dense
+ * one, which the provers commit in coefficient form, is committed here at
+ * c = 13).  A domain keeps tables for two window sizes.  out = B affine
+ * records of 9 u64.  RNG_ERR_BAD_ARG when the domain has no Lagrange bases
+ * or no table slot left. */
+int rng_commit_lagrange(RngCtx* ctx, uint64_t n, const uint64_t* evals,
+                        const uint64_t* blinders, uint32_t B, int window_c,
+                        uint64_t* out9xB);
+
 /* PlonK permutation grand product z(X) on the GPU (round 2 of the prover).
  * For proof p and row t, with w the n-th root of unity and k_j = k5[j]:
  *   num_p(t) = prod_{j<5} ( w_p[j][t] + beta_p * k_j * w^t     + gamma_p )

@@ -241,6 +241,20 @@ __host__ inline uint32_t msm_seg_cap(uint64_t total_entries) {
     return (uint32_t)cap;
 }
 
+// Cap on the compacted (Lagrange) path.  Its entries are few and skewed: a
+// settlement wire poly puts ~460 values equal to 1 into ONE bucket while the
+// other buckets hold a handful each.  msm_seg_cap of the real count gives 8,
+// and one k_msm_seg_merge lane then chains ~58 Jacobian adds; a cap of L
+// costs about L mixed adds in the reduce lane plus len/L adds in the merge
+// lane, minimal near sqrt(len) ~ 21-32 for that bucket.  Measured at the
+// settlement cohort shape, caps 8..128: 32 is the fastest.
+// Dense inputs on this path keep msm_seg_cap's larger value.
+constexpr uint32_t MSM_COMPACT_SEG_CAP = 32;
+__host__ inline uint32_t msm_compact_seg_cap(uint64_t entries) {
+    uint32_t cap = msm_seg_cap(entries);
+    return cap < MSM_COMPACT_SEG_CAP ? MSM_COMPACT_SEG_CAP : cap;
+}
+
 // ---- 3b. segment lengths + sub-segment counts ----
 // heads are in increasing order (rocprim::select is stable); seg i spans
 // [heads[i], heads[i+1] or first sentinel/total).

@@ -22,6 +22,7 @@
 #include "../../include/rng_prover.h"
 #include "ntt_kernels.hip"
 #include "msm_kernels.hip"
+#include "lagrange_kernels.hip"
 #include "plonk_kernels.hip"
 #include "perm_kernels.hip"
 #include "plonk_circuit.hpp"
@@ -238,6 +239,17 @@ struct RngCtxImpl {
         void* dev = nullptr;
     };
     FixedTable fixed_tables[3];
+    // Lagrange bases per domain size n: n + 2 affine points
+    // [L_0(tau)] .. [L_{n-1}(tau)], [tau^n] - [tau^0], [tau^(n+1)] - [tau^1],
+    // and their window tables for at most two window sizes.  Built lazily
+    // under mu; an unusable domain (a base at infinity, n + 2 > srs_count,
+    // a failed build) keeps its entry so it is not tried again.
+    struct LagrangeDomain {
+        bool usable = false;
+        void* bases = nullptr;
+        FixedTable tables[2];
+    };
+    std::map<uint64_t, LagrangeDomain> lagrange;
     uint64_t h_g2[16];       // h: x.c0,x.c1,y.c0,y.c1 Montgomery
     uint64_t beta_h_g2[16];
     std::map<uint32_t, std::unique_ptr<NttPlan>> plans;
@@ -253,6 +265,10 @@ struct RngCtxImpl {
         }
         hip_free_guarded(srs_dev);
         for (auto& t : fixed_tables) hip_free_guarded(t.dev);
+        for (auto& kv : lagrange) {
+            hip_free_guarded(kv.second.bases);
+            for (auto& t : kv.second.tables) hip_free_guarded(t.dev);
+        }
     }
 };
 
@@ -426,6 +442,7 @@ struct MsmShape {
     uint64_t n;
     uint32_t B, c;
     bool fixed;
+    bool compact;        // write and sort only the non-zero digits (Lagrange path)
     uint32_t Wd;         // digit positions per scalar
     uint32_t W;          // windows per poly as seen by buckets/aggregation/fold
     uint32_t G;          // key groups
@@ -441,13 +458,15 @@ struct MsmShape {
     uint32_t sort_bits;  // live key bits
 };
 
-static MsmShape msm_shape(uint64_t n, uint32_t B, uint32_t c, bool fixed) {
+static MsmShape msm_shape(uint64_t n, uint32_t B, uint32_t c, bool fixed,
+                          bool compact = false) {
     const MsmEnv& env = msm_env();
     MsmShape sh;
     sh.n = n;
     sh.B = B;
     sh.c = c;
     sh.fixed = fixed;
+    sh.compact = compact;
     sh.Wd = (256 + c - 1) / c;
     sh.W = fixed ? 1 : sh.Wd;
     sh.G = B * sh.W;
@@ -523,6 +542,7 @@ struct MsmScratch {
     uint64_t cap_entries = 0;
     uint64_t cap_nb = 0;
     uint64_t cap_nchunks = 0;
+    uint64_t last_entries = 0;  // entries the last run sorted (RNG_MSM_DEBUG)
 
     ~MsmScratch() {
         for (void* b : {(void*)keys_in, (void*)keys_out, (void*)vals_in, (void*)vals_out,
@@ -549,6 +569,12 @@ static int msm_scratch_ensure(const MsmShape& sh, hipStream_t stream, MsmScratch
         uint64_t cap_total = sh.total + sh.total / 2 + 64;
         uint64_t cap_nb2 = sh.nb + sh.nb / 2 + 64;
         uint64_t cap_nch = sh.nchunks + sh.nchunks / 2 + 64;
+        // never shrink a dimension: shapes that alternate on one thread (the
+        // Lagrange round at c=8: many entries, few buckets; the dense rounds
+        // at c=13: the reverse) would otherwise reallocate on every call
+        if (cap_total < s->cap_entries) cap_total = s->cap_entries;
+        if (cap_nb2 < s->cap_nb) cap_nb2 = s->cap_nb;
+        if (cap_nch < s->cap_nchunks) cap_nch = s->cap_nchunks;
         tls_msm_scratch = std::make_unique<MsmScratch>();
         s = tls_msm_scratch.get();
         HIP_CHECK(hipMalloc(&s->keys_in, cap_total * 4));
@@ -579,7 +605,9 @@ static int msm_scratch_ensure(const MsmShape& sh, hipStream_t stream, MsmScratch
             (void)rocprim::select(nullptr, s->select_temp_bytes, cit, s->head_flags,
                                   s->heads, s->head_count, sel_cap, stream);
             HIP_CHECK(hipMalloc(&s->select_temp, s->select_temp_bytes));
+            // also covers the compacted path's scan over per-scalar counts
             uint64_t scan_cap = max_heads_cap > cap_nb2 ? max_heads_cap : cap_nb2;
+            if (scan_cap < cap_total) scan_cap = cap_total;
             (void)rocprim::exclusive_scan(nullptr, s->scan_temp_bytes, s->nsub,
                                           s->sub_off, 0u, scan_cap,
                                           rocprim::plus<uint32_t>(), stream);
@@ -610,13 +638,44 @@ static int msm_scratch_ensure(const MsmShape& sh, hipStream_t stream, MsmScratch
 
 // Stage 1: digits -> radix sort -> segment heads -> capped sub-segments ->
 // reduce -> merge.  Leaves one Jacobian per bucket in s->buckets.
-static int msm_bucket_sums(const MsmShape& sh, const MsmBases& bases,
-                           const uint64_t* d_scalars, MsmScratch* s, EvtTimer& et,
-                           hipStream_t stream) {
+static int msm_bucket_sums(MsmShape sh /* by value: the compacted path shrinks total */,
+                           const MsmBases& bases, const uint64_t* d_scalars, MsmScratch* s,
+                           EvtTimer& et, hipStream_t stream) {
     const uint32_t tb = 256;
-    const uint32_t c = sh.c, total = (uint32_t)sh.total;
+    const uint32_t c = sh.c;
     const dim3 scalar_grid((uint32_t)((sh.n * sh.B + tb - 1) / tb));
-    if (sh.fixed)
+    if (sh.compact) {
+        // count -> exclusive scan -> scatter of the non-zero digits only.
+        // counts and offsets borrow vals_out / keys_out, idle until the sort.
+        const uint32_t ns = (uint32_t)(sh.n * sh.B);
+        uint32_t *counts = s->vals_out, *offs = s->keys_out;
+        hipLaunchKernelGGL(k_msm_digit_count, scalar_grid, dim3(tb), 0, stream, d_scalars,
+                           ns, c, sh.Wd, counts);
+        HIP_CHECK(hipGetLastError());
+        (void)rocprim::exclusive_scan(s->scan_temp, s->scan_temp_bytes, counts, offs, 0u, ns,
+                                      rocprim::plus<uint32_t>(), stream);
+        hipLaunchKernelGGL(k_msm_digits_compact, scalar_grid, dim3(tb), 0, stream, d_scalars,
+                           (uint32_t)sh.n, c, sh.Wd, sh.B, (uint32_t)bases.table_stride,
+                           offs, s->keys_in, s->vals_in);
+        HIP_CHECK(hipGetLastError());
+        uint32_t last_off = 0, last_cnt = 0;
+        HIP_CHECK(hipMemcpyAsync(&last_off, offs + ns - 1, 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(&last_cnt, counts + ns - 1, 4, hipMemcpyDeviceToHost,
+                                 stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        sh.total = (uint64_t)last_off + last_cnt;
+        sh.seg_cap = msm_compact_seg_cap(sh.total);
+        const int cap_env = msm_env().seg_cap;
+        if (cap_env >= 8 && cap_env <= (int)MSM_MAX_SEG) sh.seg_cap = (uint32_t)cap_env;
+        s->last_entries = sh.total;
+        if (sh.total == 0) {  // every scalar zero: identity for every poly
+            HIP_CHECK(hipMemsetAsync(s->buckets, 0, sh.nb * sizeof(G1Jac), stream));
+            et.mark(stream);
+            et.mark(stream);
+            et.mark(stream);
+            return RNG_OK;
+        }
+    } else if (sh.fixed)
         hipLaunchKernelGGL(k_msm_digits_fixed, scalar_grid, dim3(tb), 0, stream, d_scalars,
                            (uint32_t)sh.n, c, sh.Wd, sh.B, (uint32_t)bases.table_stride,
                            s->keys_in, s->vals_in);
@@ -624,6 +683,8 @@ static int msm_bucket_sums(const MsmShape& sh, const MsmBases& bases,
         hipLaunchKernelGGL(k_msm_digits, scalar_grid, dim3(tb), 0, stream, d_scalars,
                            (uint32_t)sh.n, c, sh.Wd, sh.B, s->keys_in, s->vals_in);
     HIP_CHECK(hipGetLastError());
+    if (!sh.compact) s->last_entries = sh.total;
+    const uint32_t total = (uint32_t)sh.total;
     et.mark(stream);
     rocprim::radix_sort_pairs(s->sort_temp, s->sort_temp_bytes, s->keys_in, s->keys_out,
                               s->vals_in, s->vals_out, sh.total, 0, sh.sort_bits, stream);
@@ -702,9 +763,11 @@ static int msm_window_sums(const MsmShape& sh, MsmScratch* s, EvtTimer& et,
     et.mark(stream);
     const bool scan2 = sh.cw % sh.subb == 0 && (sh.cw / sh.subb) % 64 == 0;
     if (msm_env().debug)
-        fprintf(stderr, "[msm] n=%lu B=%u c=%u chunk=%u cw=%u subb=%u combine=%s\n",
+        fprintf(stderr,
+                "[msm] n=%lu B=%u c=%u chunk=%u cw=%u subb=%u combine=%s entries=%lu%s\n",
                 (unsigned long)sh.n, sh.B, sh.c, sh.chunk_sz, sh.cw, sh.subb,
-                scan2 ? "scan2" : "v1");
+                scan2 ? "scan2" : "v1", (unsigned long)s->last_entries,
+                sh.compact ? " (compacted)" : "");
     if (scan2)  // scan-based combine: no per-chunk scalar weights
         hipLaunchKernelGGL(k_msm_window_combine2, dim3(sh.G * sh.subb), dim3(64), 0, stream,
                            s->partials, sh.c, sh.chunk_sz, sh.subb, s->window_sums);
@@ -752,8 +815,8 @@ static void msm_host_fold(const MsmShape& sh, const std::vector<G1Jac>& wsums,
 // description -> one fused pipeline; h_result[B].
 static int msm_dev_run(const MsmBases& bases, const uint64_t* d_scalars, uint64_t n,
                        uint32_t c, G1Jac* h_result, uint32_t B = 1,
-                       hipStream_t stream = RNG_STREAM) {
-    const MsmShape sh = msm_shape(n, B, c, bases.fixed());
+                       hipStream_t stream = RNG_STREAM, bool compact = false) {
+    const MsmShape sh = msm_shape(n, B, c, bases.fixed(), compact && bases.fixed());
     MsmScratch* s = nullptr;
     int rc = msm_scratch_ensure(sh, stream, &s);
     if (rc != RNG_OK) return rc;
@@ -833,6 +896,203 @@ static int msm_srs_run(RngCtxImpl* ctx, const uint64_t* d_canon, uint64_t m, uin
     uint32_t c = window_c ? (uint32_t)window_c : msm_auto_c(m);
     if ((uint64_t)B * ((256 + c - 1) / c) > 60000) return RNG_ERR_BAD_ARG;  // g<<16 cap
     return msm_dev_run(MsmBases::plain((const G1Aff*)ctx->srs_dev), d_canon, m, c, res, B);
+}
+
+// ---- Lagrange-basis commitments of evaluation vectors ----
+
+// internal status: this domain has no Lagrange bases (a base at infinity,
+// n + 2 > srs_count, no table slot or memory); provers fall back to the
+// coefficient path, the test hook reports RNG_ERR_BAD_ARG
+constexpr int MSM_LAGRANGE_UNUSABLE = -100;
+
+// bases for domain size n; called with ctx->mu held
+static int lagrange_build_bases(RngCtxImpl* ctx, uint64_t n, void** out_bases) {
+    const uint32_t N = (uint32_t)n + 2;
+    uint32_t logn = 0;
+    while ((1ull << logn) < n) ++logn;
+    const hipStream_t st = RNG_STREAM;
+    G1Jac *pts = nullptr, *fin = nullptr;
+    Fr* tw = nullptr;
+    uint32_t* bad = nullptr;
+    void* bases = nullptr;
+    auto cleanup = [&] {
+        hipFree(pts);
+        hipFree(fin);
+        hipFree(tw);
+        hipFree(bad);
+    };
+    if (hipMalloc(&pts, n * sizeof(G1Jac)) != hipSuccess ||
+        hipMalloc(&fin, (uint64_t)N * sizeof(G1Jac)) != hipSuccess ||
+        hipMalloc(&tw, (n / 2) * sizeof(Fr)) != hipSuccess ||
+        hipMalloc(&bad, 4) != hipSuccess ||
+        hipMalloc(&bases, (uint64_t)N * sizeof(G1Aff)) != hipSuccess) {
+        cleanup();
+        hipFree(bases);
+        return RNG_ERR_HIP;
+    }
+    const Fr winv = h_fr_root_of_unity((uint32_t)n).inverse();
+    Fr nfr = Fr::one();
+    for (uint32_t i = 0; i < logn; ++i) nfr = nfr.add(nfr);  // n = 2^logn
+    Canon4 ninv;
+    nfr.inverse().to_canonical(ninv.l);
+    const G1Aff* srs = (const G1Aff*)ctx->srs_dev;
+    hipMemsetAsync(bad, 0, 4, st);
+    hipLaunchKernelGGL(k_pow_table, dim3((uint32_t)((n / 2 + 255) / 256)), dim3(256), 0, st,
+                       tw, winv, (uint64_t)1, n / 2);
+    hipLaunchKernelGGL(k_g1_ntt_load, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st,
+                       srs, (uint32_t)n, pts);
+    for (uint32_t h = (uint32_t)n / 2; h >= 1; h >>= 1)
+        hipLaunchKernelGGL(k_g1_ntt_pass, dim3((uint32_t)((n / 2 + 63) / 64)), dim3(64), 0,
+                           st, pts, (uint32_t)n, h, (const Fr*)tw);
+    hipLaunchKernelGGL(k_g1_ntt_finish, dim3((N + 63) / 64), dim3(64), 0, st,
+                       (const G1Jac*)pts, srs, (uint32_t)n, logn, ninv, fin);
+    const uint32_t norm_threads = (N + LAG_NORM - 1) / LAG_NORM;
+    hipLaunchKernelGGL(k_g1_normalize, dim3((norm_threads + 63) / 64), dim3(64), 0, st,
+                       (const G1Jac*)fin, N, (G1Aff*)bases, bad);
+    uint32_t h_bad = 1;
+    bool ok = hipGetLastError() == hipSuccess &&
+              hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+              hipStreamSynchronize(st) == hipSuccess;
+    cleanup();
+    if (!ok || h_bad) {
+        hipFree(bases);
+        return ok ? MSM_LAGRANGE_UNUSABLE : RNG_ERR_HIP;
+    }
+    *out_bases = bases;
+    return RNG_OK;
+}
+
+// Window table over the Lagrange bases of domain n for window size c, both
+// built on first use.  nullptr = unusable (callers fall back).  Holds
+// ctx->mu for the builds and synchronizes before anything is published, as
+// msm_fixed_table does, so concurrent threads race to it safely.
+static const G1Aff* msm_lagrange_table(RngCtxImpl* ctx, uint64_t n, uint32_t c) {
+    if (!ctx->srs_dev || n < 2 || (n & (n - 1)) || n > (1ull << 28) ||
+        n + 2 > ctx->srs_count || c < 8 || c > 16)
+        return nullptr;
+    const uint64_t N = n + 2;
+    const uint32_t W = (256 + c - 1) / c;
+    if ((uint64_t)W * N * sizeof(G1Aff) > (1ull << 30)) return nullptr;
+    static const int trace = msm_env().debug;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto it = ctx->lagrange.find(n);
+    if (it == ctx->lagrange.end()) {
+        auto t0 = std::chrono::steady_clock::now();
+        RngCtxImpl::LagrangeDomain dom;
+        dom.usable = lagrange_build_bases(ctx, n, &dom.bases) == RNG_OK;
+        it = ctx->lagrange.emplace(n, dom).first;
+        if (trace)
+            fprintf(stderr, "[lagrange] n=%lu bases %s in %.2f ms\n", (unsigned long)n,
+                    dom.usable ? "built" : "UNUSABLE",
+                    std::chrono::duration<double, std::milli>(
+                        std::chrono::steady_clock::now() - t0).count());
+    }
+    RngCtxImpl::LagrangeDomain& dom = it->second;
+    if (!dom.usable) return nullptr;
+    for (auto& t : dom.tables)
+        if (t.dev && t.c == c) return (const G1Aff*)t.dev;
+    for (auto& t : dom.tables) {
+        if (t.dev) continue;
+        auto t0 = std::chrono::steady_clock::now();
+        void* dev = nullptr;
+        if (hipMalloc(&dev, (uint64_t)W * N * sizeof(G1Aff)) != hipSuccess) return nullptr;
+        hipLaunchKernelGGL(k_msm_fixed_table, dim3((uint32_t)((N + 255) / 256)), dim3(256),
+                           0, RNG_STREAM, (const G1Aff*)dom.bases, (uint32_t)N, c, W,
+                           (G1Aff*)dev);
+        if (hipGetLastError() != hipSuccess ||
+            hipStreamSynchronize(RNG_STREAM) != hipSuccess) {
+            hipFree(dev);
+            return nullptr;
+        }
+        t.c = c;
+        t.dev = dev;
+        if (trace)
+            fprintf(stderr, "[lagrange] n=%lu c=%u table (%.1f MB) in %.2f ms\n",
+                    (unsigned long)n, c, (double)W * N * sizeof(G1Aff) / 1e6,
+                    std::chrono::duration<double, std::milli>(
+                        std::chrono::steady_clock::now() - t0).count());
+        return (const G1Aff*)dev;
+    }
+    return nullptr;
+}
+
+// Window size on the Lagrange path.  The density figure is the share of
+// non-zero scalars, which does not depend on c.  Sparse witnesses (the
+// settlement circuit: ~19 % non-zero values, most of them one digit long)
+// leave so few entries that aggregation over B*2^(c-1) buckets is all that
+// remains, so they take the smallest table-backed window (c = 8 beat 10 and
+// 13 at the settlement cohort shape: DESIGN §4.1).  A dense witness (more
+// than half of the scalars non-zero; the validity circuits are at 86-96 %)
+// gains nothing here: 0 tells the provers to commit the coefficients as
+// before, so such a domain never builds bases or tables.  The 1/2 threshold
+// is reasoned, not tuned: the circuits sit at 19 % and at 86 % and above.
+// The test hook commits dense input at MSM_LAGRANGE_DENSE_C whatever B is,
+// so a domain sees at most two window sizes.
+constexpr uint32_t MSM_LAGRANGE_SPARSE_C = 8, MSM_LAGRANGE_DENSE_C = 13;
+static uint32_t msm_lagrange_c(uint64_t n, uint32_t B, uint64_t nonzero) {
+    return nonzero * 2 <= (uint64_t)B * n ? MSM_LAGRANGE_SPARSE_C : 0;
+}
+
+// B evaluation vectors committed against the Lagrange bases of domain n:
+// d_canon holds B blocks of n + 2 canonical scalars (n evaluations, then the
+// poly's two blinders).  Same group elements as msm_srs_run over the blinded
+// coefficients.  window_c 0 = msm_lagrange_c (RNG_MSM_C overrides); where
+// that declines a dense batch the result is MSM_LAGRANGE_UNUSABLE, unless
+// dense_too (the test hook) asks for the commitment anyway.
+static int msm_lagrange_run(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon, uint32_t B,
+                            G1Jac* res, int window_c = 0, bool dense_too = false) {
+    if (n < 2 || (n & (n - 1)) || B == 0 || !d_canon) return RNG_ERR_BAD_ARG;
+    if (n + 2 > ctx->srs_count) return MSM_LAGRANGE_UNUSABLE;
+    const int c_env = msm_env().c;
+    if (window_c == 0 && c_env >= 8 && c_env <= 16) window_c = c_env;
+    if (window_c != 0 && (window_c < 8 || window_c > 16)) return RNG_ERR_BAD_ARG;
+    uint32_t c = (uint32_t)window_c;
+    if (c == 0) {
+        MsmScratch* s = nullptr;
+        // any shape sizes the scratch; head_count doubles as the counter
+        int rc = msm_scratch_ensure(msm_shape(n + 2, B, 8, true, true), RNG_STREAM, &s);
+        if (rc != RNG_OK) return rc;
+        const uint32_t ns = (uint32_t)(B * (n + 2));
+        uint32_t nz = 0;
+        HIP_CHECK(hipMemsetAsync(s->head_count, 0, 4, RNG_STREAM));
+        hipLaunchKernelGGL(k_count_nonzero_scalars, dim3((ns + 255) / 256), dim3(256), 0,
+                           RNG_STREAM, d_canon, ns, s->head_count);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(&nz, s->head_count, 4, hipMemcpyDeviceToHost, RNG_STREAM));
+        HIP_CHECK(hipStreamSynchronize(RNG_STREAM));
+        c = msm_lagrange_c(n, B, nz);
+        if (c == 0) {
+            if (!dense_too) return MSM_LAGRANGE_UNUSABLE;
+            c = MSM_LAGRANGE_DENSE_C;
+        }
+    }
+    uint32_t gb = 1;
+    while ((1u << gb) <= B) ++gb;
+    if (c + gb > 32) return MSM_LAGRANGE_UNUSABLE;
+    const G1Aff* table = msm_lagrange_table(ctx, n, c);
+    if (!table) return MSM_LAGRANGE_UNUSABLE;
+    return msm_dev_run(MsmBases::table(table, n + 2), d_canon, n + 2, c, res, B, RNG_STREAM,
+                       true);
+}
+
+// RNG_R1_LAGRANGE, read once per process: 0 = round 1 commits the blinded
+// coefficients, 1 = commits the evaluations against the Lagrange bases in
+// both provers, unset = the per-path defaults below (the A/B behind them:
+// DESIGN §4.1, profiles/lagrange_commit_ab.json).
+constexpr bool R1_LAGRANGE_DEFAULT_SINGLE = false;
+constexpr bool R1_LAGRANGE_DEFAULT_COHORT = true;
+static int r1_lagrange_env() {
+    static const int v = [] {
+        const char* e = getenv("RNG_R1_LAGRANGE");
+        return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+    }();
+    return v;
+}
+static bool r1_lagrange_single() {
+    return r1_lagrange_env() < 0 ? R1_LAGRANGE_DEFAULT_SINGLE : r1_lagrange_env() == 1;
+}
+static bool r1_lagrange_cohort() {
+    return r1_lagrange_env() < 0 ? R1_LAGRANGE_DEFAULT_COHORT : r1_lagrange_env() == 1;
 }
 
 // Jacobian (host) -> 9-u64 affine record, using host-side field ops.
@@ -1261,6 +1521,28 @@ static int commit_staged(RngCtxImpl* ctx, uint64_t m, uint32_t B, G1Aff* out,
     return RNG_OK;
 }
 
+// round-1 commit on the Lagrange path: s->canon already holds B blocks of
+// n + 2 canonical scalars (k_lagrange_scalars).  MSM_LAGRANGE_UNUSABLE tells
+// the caller to commit the staged coefficients instead.
+static int commit_lagrange_canon(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon,
+                                 uint32_t B, G1Aff* out, bool* out_inf) {
+    std::vector<G1Jac> res(B);
+    int rc = msm_lagrange_run(ctx, n, d_canon, B, res.data());
+    if (rc != RNG_OK) return rc;
+    auto one = [&](uint32_t b) {
+        uint64_t rec[9];
+        jac_to_affine_record(res[b], rec);
+        memcpy(out[b].x.l, rec, 32);
+        memcpy(out[b].y.l, rec + 4, 32);
+        out_inf[b] = rec[8] != 0;
+    };
+    if (B >= 8)
+        HostPool::inst().parallel_for(B, one);
+    else
+        for (uint32_t b = 0; b < B; ++b) one(b);
+    return RNG_OK;
+}
+
 // k proofs in lockstep under ONE proving key (the headline shape: a stream
 // of same-circuit jobs).  Bit-identical to k calls of plonk_prove_impl with
 // the same seeds; 4 fused MSM runs per cohort instead of 5k.
@@ -1328,15 +1610,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
             HIP_CHECK(hipMemcpyAsync(cs->stage, wires_all, (size_t)5 * k * n * sizeof(Fr),
                                      hipMemcpyHostToDevice, RNG_STREAM));
         }
-        COHORT_TRACE("r1-ifft");
-        int rc = ntt_dev_run(ctx, cs->stage, cs->ntt_tmp, (uint32_t)n, 5 * (uint64_t)k,
-                             true, RNG_STREAM);
-        if (rc != RNG_OK) return rc;
-        COHORT_TRACE("r1-ifft-done");
-        // blind + pad ON DEVICE (blinders drawn host-side in the single-
-        // proof DRBG order), commit straight from the staged device buffer;
-        // the blinded coefficients stream back D2H on the same stream and
-        // are complete once the commit's internal sync returns
+        // blinders drawn host-side in the single-proof DRBG order
         std::vector<Fr> blind_h(10 * (size_t)k);
         for (uint32_t p = 0; p < k; ++p)
             for (int j = 0; j < 5; ++j) {
@@ -1346,6 +1620,25 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         HIP_CHECK(hipMemcpyAsync(cs->blinders, blind_h.data(),
                                  blind_h.size() * sizeof(Fr), hipMemcpyHostToDevice,
                                  RNG_STREAM));
+        const bool lagrange = r1_lagrange_cohort();
+        if (lagrange) {
+            // the commitment MSM reads the (sparse) evaluations and the
+            // blinders as scalars against the Lagrange bases: canonicalise
+            // them before the IFFT overwrites stage
+            uint64_t lt = 5 * (uint64_t)k * (n + 2);
+            hipLaunchKernelGGL(k_lagrange_scalars, dim3((uint32_t)((lt + 255) / 256)),
+                               dim3(256), 0, RNG_STREAM, (const Fr*)cs->stage,
+                               (const Fr*)cs->blinders, (uint32_t)n, lt, cs->canon);
+            HIP_CHECK(hipGetLastError());
+        }
+        COHORT_TRACE("r1-ifft");
+        int rc = ntt_dev_run(ctx, cs->stage, cs->ntt_tmp, (uint32_t)n, 5 * (uint64_t)k,
+                             true, RNG_STREAM);
+        if (rc != RNG_OK) return rc;
+        COHORT_TRACE("r1-ifft-done");
+        // blind + pad ON DEVICE, commit straight from the staged device
+        // buffers; the blinded coefficients stream back D2H on the same
+        // stream and are complete once the commit's internal sync returns
         uint64_t total1 = 5 * (uint64_t)k * (n + 3);
         hipLaunchKernelGGL(k_blind_wires_batch,
                            dim3((uint32_t)((total1 + 255) / 256)), dim3(256), 0,
@@ -1357,8 +1650,12 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         HIP_CHECK(hipMemcpyAsync(host_flat.data(), cs->stage, wlen * sizeof(Fr),
                                  hipMemcpyDeviceToHost, RNG_STREAM));
         COHORT_TRACE("r1-sync-done");
-        if (commit_staged(ctx, n + 2, 5 * k, cbuf.data(), ibuf.get()) != RNG_OK)
-            return RNG_ERR_HIP;
+        int crc = lagrange ? commit_lagrange_canon(ctx, n, cs->canon, 5 * k, cbuf.data(),
+                                                   ibuf.get())
+                           : MSM_LAGRANGE_UNUSABLE;
+        if (crc == MSM_LAGRANGE_UNUSABLE)  // coefficient path
+            crc = commit_staged(ctx, n + 2, 5 * k, cbuf.data(), ibuf.get());
+        if (crc != RNG_OK) return RNG_ERR_HIP;
         pool.parallel_for(k, [&](uint32_t p) {
             for (int j = 0; j < 5; ++j) {
                 auto& wp = wpoly[5 * (size_t)p + j];
@@ -1816,9 +2113,11 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
     // --- R1: wire polys ---
     std::vector<Fr> wpoly[5];
     const bool z_dev = z_device_single() && n <= PERM_MAX_N;
-    if (z_dev) {
+    const bool lagrange = r1_lagrange_single();
+    if (z_dev || lagrange) {
         // the wire evaluations go up once and stay in w_coset (free until
-        // R3) for the device grand product; the IFFT runs on a copy
+        // R3) for the device grand product and the Lagrange commit; the
+        // IFFT runs on a copy
         Fr* wev = sc->w_coset;
         HIP_CHECK(hipMemcpyAsync(wev, wires, 5 * n * sizeof(Fr), hipMemcpyHostToDevice,
                                  RNG_STREAM));
@@ -1829,8 +2128,11 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
     } else if (ifft_columns(ctx, wires, n, 5, wpoly) != RNG_OK) {
         return RNG_ERR_HIP;
     }
+    Fr blind[10];
     for (int j = 0; j < 5; ++j) {
         Fr b0 = drbg.next(), b1 = drbg.next();
+        blind[2 * j] = b0;
+        blind[2 * j + 1] = b1;
         wpoly[j].resize(n + 2, Fr::zero());
         wpoly[j][0] = wpoly[j][0].sub(b0);
         wpoly[j][1] = wpoly[j][1].sub(b1);
@@ -1838,9 +2140,25 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
         wpoly[j][n + 1] = wpoly[j][n + 1].add(b1);
     }
     {
-        const std::vector<Fr>* ps[5] = {&wpoly[0], &wpoly[1], &wpoly[2], &wpoly[3],
-                                        &wpoly[4]};
-        if (commit_dev_batch(ctx, ps, 5, comms, comm_inf) != RNG_OK) return RNG_ERR_HIP;
+        int crc = MSM_LAGRANGE_UNUSABLE;
+        if (lagrange) {
+            // commit the evaluations (still in w_coset) and the blinders
+            // against the Lagrange bases: same group elements
+            HIP_CHECK(hipMemcpyAsync(sc->stage, blind, sizeof(blind), hipMemcpyHostToDevice,
+                                     RNG_STREAM));
+            uint64_t lt = 5 * (n + 2);
+            hipLaunchKernelGGL(k_lagrange_scalars, dim3((uint32_t)((lt + 255) / 256)),
+                               dim3(256), 0, RNG_STREAM, (const Fr*)sc->w_coset,
+                               (const Fr*)sc->stage, (uint32_t)n, lt, sc->canon);
+            HIP_CHECK(hipGetLastError());
+            crc = commit_lagrange_canon(ctx, n, sc->canon, 5, comms, comm_inf);
+        }
+        if (crc == MSM_LAGRANGE_UNUSABLE) {  // coefficient path
+            const std::vector<Fr>* ps[5] = {&wpoly[0], &wpoly[1], &wpoly[2], &wpoly[3],
+                                            &wpoly[4]};
+            crc = commit_dev_batch(ctx, ps, 5, comms, comm_inf);
+        }
+        if (crc != RNG_OK) return RNG_ERR_HIP;
     }
     for (int j = 0; j < 5; ++j) tr.append_g1(comms[j], comm_inf[j]);
     if (out_link_hint) {
@@ -2415,6 +2733,36 @@ int rng_msm_srs_batch(RngCtx* ctx, const uint64_t* scalars, uint64_t n, uint32_t
     if (rc == RNG_OK)
         rc = msm_srs_run(&ctx->impl, (const uint64_t*)ds, n, B, res.data(), window_c, mode);
     hipFree(ds);
+    if (rc != RNG_OK) return rc;
+    for (uint32_t b = 0; b < B; ++b) jac_to_affine_record(res[b], out9xB + 9 * b);
+    return RNG_OK;
+}
+
+int rng_commit_lagrange(RngCtx* ctx, uint64_t n, const uint64_t* evals,
+                        const uint64_t* blinders, uint32_t B, int window_c,
+                        uint64_t* out9xB) {
+    if (!gpu_ok()) return RNG_ERR_NO_GPU;
+    if (!ctx || !evals || !out9xB || B == 0 || n < 2 || (n & (n - 1)) ||
+        n + 2 > ctx->impl.srs_count || (uint64_t)B * (n + 2) >= (1ull << 31))
+        return RNG_ERR_BAD_ARG;
+    // pack at stride n + 2 on the host: evaluations, then the two blinders
+    std::vector<uint64_t> packed((size_t)B * (n + 2) * 4, 0);
+    for (uint32_t b = 0; b < B; ++b) {
+        memcpy(&packed[(size_t)b * (n + 2) * 4], evals + (size_t)b * n * 4, n * 32);
+        if (blinders)
+            memcpy(&packed[((size_t)b * (n + 2) + n) * 4], blinders + (size_t)b * 8, 64);
+    }
+    void* ds = nullptr;
+    HIP_CHECK(hipMalloc(&ds, packed.size() * 8));
+    std::vector<G1Jac> res(B);
+    int rc = RNG_OK;
+    if (hipMemcpy(ds, packed.data(), packed.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+        rc = RNG_ERR_HIP;
+    if (rc == RNG_OK)
+        rc = msm_lagrange_run(&ctx->impl, n, (const uint64_t*)ds, B, res.data(), window_c,
+                              true);
+    hipFree(ds);
+    if (rc == MSM_LAGRANGE_UNUSABLE) return RNG_ERR_BAD_ARG;
     if (rc != RNG_OK) return rc;
     for (uint32_t b = 0; b < B; ++b) jac_to_affine_record(res[b], out9xB + 9 * b);
     return RNG_OK;

@@ -68,6 +68,9 @@ class ProverLib:
         self.lib.rng_msm_srs_batch.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_uint64,
                                                ctypes.c_uint32, ctypes.c_int,
                                                ctypes.c_int, _U64P]
+        self.lib.rng_commit_lagrange.argtypes = [ctypes.c_void_p, ctypes.c_uint64, _U64P,
+                                                 _U64P, ctypes.c_uint32, ctypes.c_int,
+                                                 _U64P]
         self.lib.rng_perm_product.argtypes = [ctypes.c_void_p, _U64P, _U64P, _U64P, _U64P,
                                               ctypes.c_uint64, ctypes.c_uint64, _U64P]
         self.lib.rng_perm_product_pk.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _U64P,
@@ -164,6 +167,25 @@ class ProverCtx:
         out = np.zeros(9 * batch, dtype=np.uint64)
         self._check(self.lib.rng_msm_srs_batch(self.h, _ptr(scalars), n, batch, window_c,
                                                mode, _ptr(out)), "rng_msm_srs_batch")
+        return out.reshape(batch, 9)
+
+    def commit_lagrange(self, evals: np.ndarray, n: int, batch: int = 1, blinders=None,
+                        window_c: int = 0):
+        """The provers' round-1 commitment on the Lagrange path: `batch`
+        evaluation vectors of n canonical scalars each (4*n*batch u64) and,
+        optionally, two canonical blinders per vector (8*batch u64).
+        Returns a (batch, 9) array of affine records."""
+        assert evals.dtype == np.uint64 and evals.size == 4 * n * batch
+        evals = np.ascontiguousarray(evals).reshape(-1)
+        bptr = None
+        if blinders is not None:
+            assert blinders.dtype == np.uint64 and blinders.size == 8 * batch
+            blinders = np.ascontiguousarray(blinders).reshape(-1)
+            bptr = _ptr(blinders)
+        out = np.zeros(9 * batch, dtype=np.uint64)
+        self._check(self.lib.rng_commit_lagrange(self.h, n, _ptr(evals), bptr, batch,
+                                                 window_c, _ptr(out)),
+                    "rng_commit_lagrange")
         return out.reshape(batch, 9)
 
     Z_AUTO, Z_DEVICE, Z_HOST = 0, 1, 2
