@@ -4,6 +4,12 @@
 // semantics of crates/circuits/circuit-types/src/primitives/srs.rs:63-214),
 // NTT plans, MSM pipeline.  Single translation unit: includes the kernel
 // files directly.
+//
+// The two prove functions here are the device choreography of their path
+// only.  The round logic they share with each other and with rng_verify
+// (per-proof state, blinder order, R4 + R5, linearization scalars,
+// serialization, affine records) lives in plonk_rounds.hpp; the
+// circuit-construction ABI lives in circuit_abi.hpp.
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -27,6 +33,7 @@
 #include "perm_kernels.hip"
 #include "plonk_circuit.hpp"
 #include "plonk_host.hpp"
+#include "plonk_rounds.hpp"
 #include "test_circuits.hpp"
 #include "circuits_core.hpp"
 #include "pairing_impl.hpp"
@@ -420,6 +427,28 @@ static const MsmEnv& msm_env() {
         return MsmEnv{get("RNG_MSM_FIXED", 1),  get("RNG_MSM_C", 0),
                       get("RNG_MSM_CHUNK", 0),  get("RNG_MSM_SUBB", 0),
                       get("RNG_MSM_SEGCAP", 0), get("RNG_MSM_DEBUG", 0)};
+    }();
+    return env;
+}
+
+// The prover's own switches, read once per process.  z_device and
+// r1_lagrange: -1 = unset (the per-path *_DEFAULT_* constants decide), 0 =
+// off, 1 = on in both provers.
+struct ProverEnv {
+    int z_device;      // RNG_Z_DEVICE: R2 grand product on the device
+    int r1_lagrange;   // RNG_R1_LAGRANGE: R1 commits in the Lagrange basis
+    int cohort_trace;  // RNG_COHORT_TRACE: stderr timeline of a cohort
+    static bool on(int v, bool path_default) { return v < 0 ? path_default : v == 1; }
+};
+
+static const ProverEnv& prover_env() {
+    static const ProverEnv env = [] {
+        auto tri = [](const char* name) {
+            const char* e = getenv(name);
+            return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+        };
+        const char* t = getenv("RNG_COHORT_TRACE");
+        return ProverEnv{tri("RNG_Z_DEVICE"), tri("RNG_R1_LAGRANGE"), t ? atoi(t) : 0};
     }();
     return env;
 }
@@ -1075,41 +1104,12 @@ static int msm_lagrange_run(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon
                        true);
 }
 
-// RNG_R1_LAGRANGE, read once per process: 0 = round 1 commits the blinded
+// RNG_R1_LAGRANGE (ProverEnv::r1_lagrange): 0 = round 1 commits the blinded
 // coefficients, 1 = commits the evaluations against the Lagrange bases in
 // both provers, unset = the per-path defaults below (the A/B behind them:
 // DESIGN §4.1, profiles/lagrange_commit_ab.json).
 constexpr bool R1_LAGRANGE_DEFAULT_SINGLE = false;
 constexpr bool R1_LAGRANGE_DEFAULT_COHORT = true;
-static int r1_lagrange_env() {
-    static const int v = [] {
-        const char* e = getenv("RNG_R1_LAGRANGE");
-        return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-    }();
-    return v;
-}
-static bool r1_lagrange_single() {
-    return r1_lagrange_env() < 0 ? R1_LAGRANGE_DEFAULT_SINGLE : r1_lagrange_env() == 1;
-}
-static bool r1_lagrange_cohort() {
-    return r1_lagrange_env() < 0 ? R1_LAGRANGE_DEFAULT_COHORT : r1_lagrange_env() == 1;
-}
-
-// Jacobian (host) -> 9-u64 affine record, using host-side field ops.
-static void jac_to_affine_record(const G1Jac& j, uint64_t* out9) {
-    if (j.Z.is_zero()) {
-        memset(out9, 0, 9 * 8);
-        out9[8] = 1;
-        return;
-    }
-    Fq zinv = j.Z.inverse();
-    Fq zinv2 = zinv.sqr();
-    Fq x = j.X.mul(zinv2);
-    Fq y = j.Y.mul(zinv2.mul(zinv));
-    memcpy(out9, x.l, 32);
-    memcpy(out9 + 4, y.l, 32);
-    out9[8] = 0;
-}
 
 // ---------------- TurboPlonk prover (GPU) ----------------
 
@@ -1173,13 +1173,7 @@ struct ProveScratch {  // per-context device scratch for proving at size n
     }
 };
 
-struct PlonkPkImpl {
-    uint64_t n = 0, npub = 0;
-    Fr k[5];
-    std::vector<Fr> selq[13], sigp[5];       // host coeffs
-    std::vector<Fr> sig_evals[5];            // host evals (z build)
-    G1Aff sel_comms[13], sig_comms[5];
-    bool sel_inf[13] = {false}, sig_inf[5] = {false};
+struct PlonkPkImpl : PlonkPkHost {  // host half: plonk_rounds.hpp
     Fr* sel_coset = nullptr;   // device 13*m
     Fr* sig_coset = nullptr;   // device 5*m
     Fr* l1_coset = nullptr;    // device m
@@ -1214,24 +1208,11 @@ static int prove_scratch_ensure(uint64_t n) {
 
 // ---------------- R2: permutation grand product ----------------
 
-// RNG_Z_DEVICE, read once per process: 0 = host loops, 1 = device stage
+// RNG_Z_DEVICE (ProverEnv::z_device): 0 = host loops, 1 = device stage
 // (perm_kernels.hip) in both provers.  Unset: per-path defaults below, set
 // by the A/B measurement in DESIGN.md §4.5.
 constexpr bool Z_DEVICE_DEFAULT_SINGLE = true;
 constexpr bool Z_DEVICE_DEFAULT_COHORT = true;
-static int z_device_env() {
-    static const int v = [] {
-        const char* e = getenv("RNG_Z_DEVICE");
-        return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-    }();
-    return v;
-}
-static bool z_device_single() {
-    return z_device_env() < 0 ? Z_DEVICE_DEFAULT_SINGLE : z_device_env() == 1;
-}
-static bool z_device_cohort() {
-    return z_device_env() < 0 ? Z_DEVICE_DEFAULT_COHORT : z_device_env() == 1;
-}
 
 // host loop: n evaluations of one proof's z into ze
 static void perm_product_host(const PlonkPkImpl& pk, const Fr& w, const Fr* wires,
@@ -1347,6 +1328,19 @@ static int perm_product_dev(const Fr* wires, const Fr* sigma, const Fr* wpow,
     return RNG_OK;
 }
 
+// tail of a KZG commit: B polys of m Montgomery coefficients staged on the
+// device -> canonical scalars -> ONE fused MSM over the SRS bases.  The
+// callers turn the Jacobian results affine in a loop of their own.
+static int commit_staged_jac(RngCtxImpl* ctx, const Fr* stage, uint64_t* canon, uint64_t m,
+                             uint32_t B, G1Jac* res) {
+    uint32_t blocks = (uint32_t)((B * m + 255) / 256);
+    hipLaunchKernelGGL(k_fr_to_canonical, dim3(blocks), dim3(256), 0, RNG_STREAM, stage,
+                       canon, (uint32_t)(B * m));
+    HIP_CHECK(hipGetLastError());
+    // window size: auto by problem size; RNG_MSM_C overrides for tuning
+    return msm_srs_run(ctx, canon, m, B, res);
+}
+
 // commit to B host coefficient vectors via ONE fused GPU MSM over the SRS
 // bases (shorter polys zero-padded; zero scalars cost nothing)
 static int commit_dev_batch(RngCtxImpl* ctx, const std::vector<Fr>* const* polys,
@@ -1361,21 +1355,10 @@ static int commit_dev_batch(RngCtxImpl* ctx, const std::vector<Fr>* const* polys
         HIP_CHECK(hipMemcpyAsync(s->stage + b * m, polys[b]->data(),
                                  polys[b]->size() * sizeof(Fr), hipMemcpyHostToDevice,
                                  RNG_STREAM));
-    uint32_t blocks = (uint32_t)((B * m + 255) / 256);
-    hipLaunchKernelGGL(k_fr_to_canonical, dim3(blocks), dim3(256), 0, RNG_STREAM,
-                       s->stage, s->canon, (uint32_t)(B * m));
-    HIP_CHECK(hipGetLastError());
     G1Jac res[13];
-    // window size: auto by problem size; RNG_MSM_C overrides for tuning
-    int rc = msm_srs_run(ctx, s->canon, m, B, res);
+    int rc = commit_staged_jac(ctx, s->stage, s->canon, m, B, res);
     if (rc != RNG_OK) return rc;
-    for (uint32_t b = 0; b < B; ++b) {
-        uint64_t rec[9];
-        jac_to_affine_record(res[b], rec);
-        memcpy(out[b].x.l, rec, 32);
-        memcpy(out[b].y.l, rec + 4, 32);
-        out_inf[b] = rec[8] != 0;
-    }
+    for (uint32_t b = 0; b < B; ++b) jac_to_affine(res[b], &out[b], &out_inf[b]);
     return RNG_OK;
 }
 
@@ -1392,13 +1375,12 @@ static int commit_dev(RngCtxImpl* ctx, const std::vector<Fr>& coeffs, G1Aff* out
 // seg_merge 22% of proof-workload GPU time), so the cohort prover advances
 // k proofs in LOCKSTEP — R1 for all, R2 for all, … — and fuses each round's
 // commitments into ONE msm_dev_run (key group g = poly*W + window already
-// supports a batch dimension).  Transcripts and blinders stay per-proof
-// (each transcript consumes only its own commitments), so cohort proofs are
+// supports a batch dimension).  Transcripts and blinders stay per-proof (one
+// ProofState each, which consumes only its own commitments) and the host
+// rounds are plonk_prove_impl's own (plonk_rounds.hpp), so cohort proofs are
 // bit-identical to rng_prove with the same seed.  Host-side phases (grand
 // product, evaluations, linearization) run on a persistent worker pool
 // (HostPool, defined before msm_dev_run so its window fold can use it).
-
-static void h_transcript_init(HostTranscript& tr, const PlonkPkImpl& pk, const Fr* pubs);
 
 struct CohortScratch {  // per-thread device scratch for cohort proving
     uint64_t n = 0, k = 0;
@@ -1455,10 +1437,7 @@ static int commit_staged(RngCtxImpl* ctx, uint64_t m, uint32_t B, G1Aff* out,
 // conversion are parallelized across the pool for large B.
 static int commit_cohort(RngCtxImpl* ctx, const std::vector<Fr>* const* polys,
                          uint32_t B, G1Aff* out, bool* out_inf) {
-    static int trace = [] {
-        const char* e = getenv("RNG_COHORT_TRACE");
-        return e ? atoi(e) : 0;
-    }();
+    const int trace = prover_env().cohort_trace;
     auto tr = [&](const char* tag) {
         if (trace) {
             fprintf(stderr, "[commit_cohort B=%u] %s\n", B, tag);
@@ -1504,20 +1483,11 @@ static int commit_staged(RngCtxImpl* ctx, uint64_t m, uint32_t B, G1Aff* out,
                          bool* out_inf) {
     CohortScratch* s = tls_cohort_scratch.get();
     if (m > ctx->srs_count) return RNG_ERR_BAD_ARG;
-    uint32_t blocks = (uint32_t)((B * m + 255) / 256);
-    hipLaunchKernelGGL(k_fr_to_canonical, dim3(blocks), dim3(256), 0, RNG_STREAM,
-                       s->stage, s->canon, (uint32_t)(B * m));
-    HIP_CHECK(hipGetLastError());
     std::vector<G1Jac> res(B);
-    int rc = msm_srs_run(ctx, s->canon, m, B, res.data());
+    int rc = commit_staged_jac(ctx, s->stage, s->canon, m, B, res.data());
     if (rc != RNG_OK) return rc;
-    HostPool::inst().parallel_for(B, [&](uint32_t b) {
-        uint64_t rec[9];
-        jac_to_affine_record(res[b], rec);
-        memcpy(out[b].x.l, rec, 32);
-        memcpy(out[b].y.l, rec + 4, 32);
-        out_inf[b] = rec[8] != 0;
-    });
+    HostPool::inst().parallel_for(
+        B, [&](uint32_t b) { jac_to_affine(res[b], &out[b], &out_inf[b]); });
     return RNG_OK;
 }
 
@@ -1529,13 +1499,7 @@ static int commit_lagrange_canon(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_
     std::vector<G1Jac> res(B);
     int rc = msm_lagrange_run(ctx, n, d_canon, B, res.data());
     if (rc != RNG_OK) return rc;
-    auto one = [&](uint32_t b) {
-        uint64_t rec[9];
-        jac_to_affine_record(res[b], rec);
-        memcpy(out[b].x.l, rec, 32);
-        memcpy(out[b].y.l, rec + 4, 32);
-        out_inf[b] = rec[8] != 0;
-    };
+    auto one = [&](uint32_t b) { jac_to_affine(res[b], &out[b], &out_inf[b]); };
     if (B >= 8)
         HostPool::inst().parallel_for(B, one);
     else
@@ -1543,9 +1507,36 @@ static int commit_lagrange_canon(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_
     return RNG_OK;
 }
 
+// the quotient kernels' challenge pack: the part fixed by the key (coset
+// shifts, 1/Z_H on the 8 cosets of the 8n domain), then one proof's challenges
+static QuotChal quot_chal_fixed(const PlonkPkImpl& pk) {
+    QuotChal ch{};
+    for (int j = 0; j < 5; ++j) ch.k[j] = pk.k[j];
+    Fr g = Fr::from_u64(FR_GENERATOR);
+    Fr gn = g.pow_u64(pk.n);
+    Fr w8 = h_fr_root_of_unity((uint32_t)(8 * pk.n)).pow_u64(pk.n);
+    std::vector<Fr> zh(8);
+    Fr cur = gn;
+    for (int t = 0; t < 8; ++t) {
+        zh[t] = cur.sub(Fr::one());
+        cur = cur.mul(w8);
+    }
+    zh = hbatch_inverse(zh);
+    for (int t = 0; t < 8; ++t) ch.zh_inv[t] = zh[t];
+    return ch;
+}
+static void quot_chal_set(QuotChal& ch, const ProofState& st) {
+    ch.beta = st.beta;
+    ch.gamma = st.gamma;
+    ch.alpha = st.alpha;
+    ch.alpha2 = st.alpha.sqr();
+}
+
 // k proofs in lockstep under ONE proving key (the headline shape: a stream
 // of same-circuit jobs).  Bit-identical to k calls of plonk_prove_impl with
-// the same seeds; 4 fused MSM runs per cohort instead of 5k.
+// the same seeds by construction: both fill a ProofState per proof and run
+// the shared host rounds of plonk_rounds.hpp on it.  4 fused MSM runs per
+// cohort instead of 5k.
 static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint32_t k,
                                    const Fr* wires_all, const Fr* pubs_all,
                                    const uint64_t* seeds, uint64_t* out_proofs,
@@ -1553,10 +1544,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     const uint64_t n = pk.n;
     const uint32_t m = (uint32_t)(8 * n);
     const uint64_t hint_u64s = 4 * (n + 2) + 9;
-    static int trace = [] {
-        const char* e = getenv("RNG_COHORT_TRACE");
-        return e ? atoi(e) : 0;
-    }();
+    const int trace = prover_env().cohort_trace;
     auto t_enter = std::chrono::steady_clock::now();
 #define COHORT_TRACE(tag)                                                     \
     do {                                                                      \
@@ -1574,19 +1562,20 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     CohortScratch* cs = tls_cohort_scratch.get();
     HostPool& pool = HostPool::inst();
     Fr w = h_fr_root_of_unity((uint32_t)n);
-    const bool z_dev = z_device_cohort() && n <= PERM_MAX_N;
+    const bool z_dev =
+        ProverEnv::on(prover_env().z_device, Z_DEVICE_DEFAULT_COHORT) && n <= PERM_MAX_N;
 
-    std::vector<HostDrbg> drbg;
-    drbg.reserve(k);
-    std::vector<HostTranscript> tr(k);
-    for (uint32_t p = 0; p < k; ++p) {
-        drbg.emplace_back(seeds[p]);
-        h_transcript_init(tr[p], pk, pubs_all + (size_t)p * pk.npub);
-    }
-    std::vector<std::vector<Fr>> wpoly(5 * (size_t)k), zpoly(k), quot_chunks(5 * (size_t)k);
-    std::vector<G1Aff> comms(13 * (size_t)k);
-    std::vector<uint8_t> cinf(13 * (size_t)k, 0);
-    std::vector<Fr> beta(k), gamma(k), alpha(k), zeta(k), vch(k);
+    std::vector<ProofState> st;
+    st.reserve(k);
+    for (uint32_t p = 0; p < k; ++p)
+        st.emplace_back(pk, pubs_all + (size_t)p * pk.npub, seeds[p]);
+    // one round's blinders of every proof, packed for the upload
+    auto pack_blinders = [&](int first, int count) {
+        std::vector<Fr> h((size_t)count * k);
+        for (uint32_t p = 0; p < k; ++p)
+            for (int i = 0; i < count; ++i) h[(size_t)count * p + i] = st[p].blind[first + i];
+        return h;
+    };
 
     // scratch for commit outputs (bool arrays for commit_cohort)
     std::vector<G1Aff> cbuf(5 * (size_t)k);
@@ -1610,17 +1599,12 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
             HIP_CHECK(hipMemcpyAsync(cs->stage, wires_all, (size_t)5 * k * n * sizeof(Fr),
                                      hipMemcpyHostToDevice, RNG_STREAM));
         }
-        // blinders drawn host-side in the single-proof DRBG order
-        std::vector<Fr> blind_h(10 * (size_t)k);
-        for (uint32_t p = 0; p < k; ++p)
-            for (int j = 0; j < 5; ++j) {
-                blind_h[10 * (size_t)p + 2 * j] = drbg[p].next();
-                blind_h[10 * (size_t)p + 2 * j + 1] = drbg[p].next();
-            }
+        std::vector<Fr> blind_h = pack_blinders(BLIND_WIRES, 10);
         HIP_CHECK(hipMemcpyAsync(cs->blinders, blind_h.data(),
                                  blind_h.size() * sizeof(Fr), hipMemcpyHostToDevice,
                                  RNG_STREAM));
-        const bool lagrange = r1_lagrange_cohort();
+        const bool lagrange =
+            ProverEnv::on(prover_env().r1_lagrange, R1_LAGRANGE_DEFAULT_COHORT);
         if (lagrange) {
             // the commitment MSM reads the (sparse) evaluations and the
             // blinders as scalars against the Lagrange bases: canonicalise
@@ -1658,29 +1642,16 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         if (crc != RNG_OK) return RNG_ERR_HIP;
         pool.parallel_for(k, [&](uint32_t p) {
             for (int j = 0; j < 5; ++j) {
-                auto& wp = wpoly[5 * (size_t)p + j];
                 const Fr* src = host_flat.data() + ((size_t)5 * p + j) * (n + 2);
-                wp.assign(src, src + (n + 2));
+                st[p].wpoly[j].assign(src, src + (n + 2));
             }
         });
         COHORT_TRACE("r1-blind-done");
         pool.parallel_for(k, [&](uint32_t p) {
-            for (int j = 0; j < 5; ++j) {
-                comms[13 * (size_t)p + j] = cbuf[5 * (size_t)p + j];
-                cinf[13 * (size_t)p + j] = ibuf[5 * (size_t)p + j] ? 1 : 0;
-                tr[p].append_g1(comms[13 * (size_t)p + j],
-                                cinf[13 * (size_t)p + j] != 0);
-            }
-            if (out_hints) {
-                uint64_t* h = out_hints + (size_t)p * hint_u64s;
-                memcpy(h, wpoly[5 * (size_t)p].data(), (n + 2) * sizeof(Fr));
-                uint64_t* c = h + 4 * (n + 2);
-                memcpy(c, comms[13 * (size_t)p].x.l, 32);
-                memcpy(c + 4, comms[13 * (size_t)p].y.l, 32);
-                c[8] = cinf[13 * (size_t)p] ? 1 : 0;
-            }
-            beta[p] = tr[p].challenge();
-            gamma[p] = tr[p].challenge();
+            st[p].take_comms(COMM_WIRES, 5, &cbuf[5 * (size_t)p], &ibuf[5 * (size_t)p]);
+            if (out_hints) st[p].write_link_hint(out_hints + (size_t)p * hint_u64s);
+            st[p].beta = st[p].tr.challenge();
+            st[p].gamma = st[p].tr.challenge();
         });
     }
 
@@ -1695,8 +1666,8 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         Fr* pi_base = evals_flat.data() + (z_dev ? 0 : (size_t)k * n);
         pool.parallel_for(k, [&](uint32_t p) {
             if (!z_dev)
-                perm_product_host(pk, w, wires_all + (size_t)5 * p * n, beta[p], gamma[p],
-                                  evals_flat.data() + (size_t)p * n);
+                perm_product_host(pk, w, wires_all + (size_t)5 * p * n, st[p].beta,
+                                  st[p].gamma, evals_flat.data() + (size_t)p * n);
             Fr* pie = pi_base + (size_t)p * n;
             for (uint64_t i = 0; i < n; ++i) pie[i] = Fr::zero();
             const Fr* pubs = pubs_all + (size_t)p * pk.npub;
@@ -1705,8 +1676,8 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         if (z_dev) {
             std::vector<Fr> bg(2 * (size_t)k);
             for (uint32_t p = 0; p < k; ++p) {
-                bg[2 * (size_t)p] = beta[p];
-                bg[2 * (size_t)p + 1] = gamma[p];
+                bg[2 * (size_t)p] = st[p].beta;
+                bg[2 * (size_t)p + 1] = st[p].gamma;
             }
             int prc = perm_product_dev(cs->coset_out, pk.sig_evals_dev, pk.wpow_dev, pk.k,
                                        bg.data(), n, k, cs->q_all, cs->stage);
@@ -1723,14 +1694,8 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
                              true, RNG_STREAM);
         if (rc != RNG_OK) return rc;
         // device-side z blinding + PI staging straight into the R3 coset
-        // slots (the wires landed there in R1); blinders in the single-proof
-        // DRBG order (b2, b3, b4)
-        std::vector<Fr> zblind_h(3 * (size_t)k);
-        for (uint32_t p = 0; p < k; ++p) {
-            zblind_h[3 * (size_t)p] = drbg[p].next();
-            zblind_h[3 * (size_t)p + 1] = drbg[p].next();
-            zblind_h[3 * (size_t)p + 2] = drbg[p].next();
-        }
+        // slots (the wires landed there in R1)
+        std::vector<Fr> zblind_h = pack_blinders(BLIND_Z, 3);
         HIP_CHECK(hipMemcpyAsync(cs->blinders, zblind_h.data(),
                                  zblind_h.size() * sizeof(Fr),
                                  hipMemcpyHostToDevice, RNG_STREAM));
@@ -1752,11 +1717,9 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         // commit_staged synchronized: z_host is complete
         pool.parallel_for(k, [&](uint32_t p) {
             const Fr* src = z_host.data() + (size_t)p * (n + 3);
-            zpoly[p].assign(src, src + (n + 3));
-            comms[13 * (size_t)p + 5] = cbuf[p];
-            cinf[13 * (size_t)p + 5] = ibuf[p] ? 1 : 0;
-            tr[p].append_g1(cbuf[p], ibuf[p]);
-            alpha[p] = tr[p].challenge();
+            st[p].zpoly.assign(src, src + (n + 3));
+            st[p].take_comms(COMM_Z, 1, &cbuf[p], &ibuf[p]);
+            st[p].alpha = st[p].tr.challenge();
         });
     }
 
@@ -1781,32 +1744,12 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
                              RNG_STREAM);
         if (rc != RNG_OK) return rc;
 
-        QuotChal ch;
-        for (int j = 0; j < 5; ++j) ch.k[j] = pk.k[j];
-        {
-            Fr g = Fr::from_u64(FR_GENERATOR);
-            Fr gn = g.pow_u64(n);
-            Fr w8 = h_fr_root_of_unity(m).pow_u64(n);
-            std::vector<Fr> zh(8);
-            Fr cur = gn;
-            for (int t = 0; t < 8; ++t) {
-                zh[t] = cur.sub(Fr::one());
-                cur = cur.mul(w8);
-            }
-            zh = hbatch_inverse(zh);
-            for (int t = 0; t < 8; ++t) ch.zh_inv[t] = zh[t];
-        }
         // ONE batched quotient launch for all k proofs (a single proof's m
         // grid is latency-starved; 483 small launches were 14% of cohort GPU
         // time in the r02 profile)
         {
-            std::vector<QuotChal> chs_h(k, ch);
-            for (uint32_t p = 0; p < k; ++p) {
-                chs_h[p].beta = beta[p];
-                chs_h[p].gamma = gamma[p];
-                chs_h[p].alpha = alpha[p];
-                chs_h[p].alpha2 = alpha[p].sqr();
-            }
+            std::vector<QuotChal> chs_h(k, quot_chal_fixed(pk));
+            for (uint32_t p = 0; p < k; ++p) quot_chal_set(chs_h[p], st[p]);
             HIP_CHECK(hipMemcpyAsync(cs->chs, chs_h.data(), k * sizeof(QuotChal),
                                      hipMemcpyHostToDevice, RNG_STREAM));
             uint64_t total_kq = (uint64_t)k * m;
@@ -1828,9 +1771,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         // chunk-split + linking blinders ON DEVICE, commit from the staged
         // buffer; the blinded chunks stream back D2H for the host R5
         // linearization (complete after the commit's internal sync)
-        std::vector<Fr> qblind_h(4 * (size_t)k);
-        for (uint32_t p = 0; p < k; ++p)
-            for (int i = 0; i < 4; ++i) qblind_h[4 * (size_t)p + i] = drbg[p].next();
+        std::vector<Fr> qblind_h = pack_blinders(BLIND_CHUNKS, 4);
         HIP_CHECK(hipMemcpyAsync(cs->blinders, qblind_h.data(),
                                  qblind_h.size() * sizeof(Fr),
                                  hipMemcpyHostToDevice, RNG_STREAM));
@@ -1848,90 +1789,20 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
             return RNG_ERR_HIP;
         pool.parallel_for(k, [&](uint32_t p) {
             for (int i = 0; i < 5; ++i) {
-                auto& qc = quot_chunks[5 * (size_t)p + i];
                 const Fr* src = chunks_host.data() + (5 * (size_t)p + i) * (n + 3);
-                qc.assign(src, src + (i < 4 ? n + 3 : n + 2));
+                st[p].quot_chunks[i].assign(src, src + (i < 4 ? n + 3 : n + 2));
             }
         });
         pool.parallel_for(k, [&](uint32_t p) {
-            for (int i = 0; i < 5; ++i) {
-                comms[13 * (size_t)p + 6 + i] = cbuf[5 * (size_t)p + i];
-                cinf[13 * (size_t)p + 6 + i] = ibuf[5 * (size_t)p + i] ? 1 : 0;
-                tr[p].append_g1(cbuf[5 * (size_t)p + i], ibuf[5 * (size_t)p + i]);
-            }
-            zeta[p] = tr[p].challenge();
+            st[p].take_comms(COMM_CHUNKS, 5, &cbuf[5 * (size_t)p], &ibuf[5 * (size_t)p]);
+            st[p].zeta = st[p].tr.challenge();
         });
     }
 
     COHORT_TRACE("r4r5");
     // --- R4 + R5: evaluations, linearization, openings (host pool) ---
     std::vector<std::vector<Fr>> Wz(k), Wzw(k);
-    std::vector<Fr> wire_evals(5 * (size_t)k), sigma_evals(4 * (size_t)k), zshift(k);
-    pool.parallel_for(k, [&](uint32_t p) {
-        Fr we[5], se[4];
-        for (int j = 0; j < 5; ++j) {
-            we[j] = hpoly_eval(wpoly[5 * (size_t)p + j], zeta[p]);
-            tr[p].append_fr(we[j]);
-            wire_evals[5 * (size_t)p + j] = we[j];
-        }
-        for (int j = 0; j < 4; ++j) {
-            se[j] = hpoly_eval(pk.sigp[j], zeta[p]);
-            tr[p].append_fr(se[j]);
-            sigma_evals[4 * (size_t)p + j] = se[j];
-        }
-        Fr zs = hpoly_eval(zpoly[p], zeta[p].mul(w));
-        zshift[p] = zs;
-        tr[p].append_fr(zs);
-        Fr v = tr[p].challenge();
-        vch[p] = v;
-
-        Fr zeta_n = zeta[p].pow_u64(n);
-        Fr zh_zeta = zeta_n.sub(Fr::one());
-        Fr l1_zeta = zh_zeta.mul(Fr::from_u64(n).mul(zeta[p].sub(Fr::one())).inverse());
-        auto p5f = [](const Fr& x) {
-            Fr x2 = x.sqr();
-            return x2.sqr().mul(x);
-        };
-        const Fr* wb = we;
-        std::vector<Fr> D;
-        hpoly_add_scaled(D, pk.selq[11], Fr::one());
-        for (int j = 0; j < 4; ++j) hpoly_add_scaled(D, pk.selq[j], wb[j]);
-        hpoly_add_scaled(D, pk.selq[4], wb[0].mul(wb[1]));
-        hpoly_add_scaled(D, pk.selq[5], wb[2].mul(wb[3]));
-        for (int j = 0; j < 4; ++j) hpoly_add_scaled(D, pk.selq[6 + j], p5f(wb[j]));
-        hpoly_add_scaled(D, pk.selq[12],
-                         wb[0].mul(wb[1]).mul(wb[2]).mul(wb[3]).mul(wb[4]));
-        hpoly_add_scaled(D, pk.selq[10], wb[4].neg());
-        Fr fbar = Fr::one(), Bbar = Fr::one();
-        for (int j = 0; j < 5; ++j)
-            fbar = fbar.mul(wb[j].add(beta[p].mul(pk.k[j]).mul(zeta[p])).add(gamma[p]));
-        for (int j = 0; j < 4; ++j)
-            Bbar = Bbar.mul(wb[j].add(beta[p].mul(se[j])).add(gamma[p]));
-        hpoly_add_scaled(D, zpoly[p],
-                         alpha[p].mul(fbar).add(alpha[p].sqr().mul(l1_zeta)));
-        hpoly_add_scaled(D, pk.sigp[4],
-                         alpha[p].mul(beta[p]).mul(zs).mul(Bbar).neg());
-        {
-            Fr zpow = zh_zeta.neg();
-            Fr step = zeta[p].pow_u64(n + 2);
-            for (int i = 0; i < 5; ++i) {
-                hpoly_add_scaled(D, quot_chunks[5 * (size_t)p + i], zpow);
-                zpow = zpow.mul(step);
-            }
-        }
-        std::vector<Fr> C = D;
-        Fr vp = Fr::one();
-        for (int j = 0; j < 5; ++j) {
-            vp = vp.mul(v);
-            hpoly_add_scaled(C, wpoly[5 * (size_t)p + j], vp);
-        }
-        for (int j = 0; j < 4; ++j) {
-            vp = vp.mul(v);
-            hpoly_add_scaled(C, pk.sigp[j], vp);
-        }
-        Wz[p] = hpoly_div_linear(C, zeta[p]);
-        Wzw[p] = hpoly_div_linear(zpoly[p], zeta[p].mul(w));
-    });
+    pool.parallel_for(k, [&](uint32_t p) { rounds_4_5(pk, w, st[p], Wz[p], Wzw[p]); });
     for (uint32_t p = 0; p < k; ++p) {
         ps[2 * (size_t)p] = &Wz[p];
         ps[2 * (size_t)p + 1] = &Wzw[p];
@@ -1939,25 +1810,8 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     if (commit_cohort(ctx, ps.data(), 2 * k, cbuf.data(), ibuf.get()) != RNG_OK)
         return RNG_ERR_HIP;
     pool.parallel_for(k, [&](uint32_t p) {
-        comms[13 * (size_t)p + 11] = cbuf[2 * (size_t)p];
-        cinf[13 * (size_t)p + 11] = ibuf[2 * (size_t)p] ? 1 : 0;
-        comms[13 * (size_t)p + 12] = cbuf[2 * (size_t)p + 1];
-        cinf[13 * (size_t)p + 12] = ibuf[2 * (size_t)p + 1] ? 1 : 0;
-        tr[p].append_g1(cbuf[2 * (size_t)p], ibuf[2 * (size_t)p]);
-        tr[p].append_g1(cbuf[2 * (size_t)p + 1], ibuf[2 * (size_t)p + 1]);
-        // --- serialize ---
-        uint64_t* out_proof = out_proofs + (size_t)p * 157;
-        for (int i = 0; i < 13; ++i) {
-            memcpy(out_proof + 9 * i, comms[13 * (size_t)p + i].x.l, 32);
-            memcpy(out_proof + 9 * i + 4, comms[13 * (size_t)p + i].y.l, 32);
-            out_proof[9 * i + 8] = cinf[13 * (size_t)p + i] ? 1 : 0;
-        }
-        uint64_t* e = out_proof + 117;
-        for (int i = 0; i < 5; ++i)
-            memcpy(e + 4 * i, wire_evals[5 * (size_t)p + i].l, 32);
-        for (int i = 0; i < 4; ++i)
-            memcpy(e + 20 + 4 * i, sigma_evals[4 * (size_t)p + i].l, 32);
-        memcpy(e + 36, zshift[p].l, 32);
+        st[p].take_comms(COMM_WZ, 2, &cbuf[2 * (size_t)p], &ibuf[2 * (size_t)p]);
+        st[p].serialize(out_proofs + (size_t)p * 157);
     });
     return RNG_OK;
 }
@@ -2086,15 +1940,8 @@ static int plonk_preprocess_impl(RngCtxImpl* ctx, const RngCircuitDesc* d,
     return RNG_OK;
 }
 
-// transcript init shared with the verifier side (spec: oracle/transcript.hpp)
-static void h_transcript_init(HostTranscript& tr, const PlonkPkImpl& pk, const Fr* pubs) {
-    tr.append_u64(pk.n);
-    tr.append_u64(pk.npub);
-    for (int s = 0; s < 13; ++s) tr.append_g1(pk.sel_comms[s], pk.sel_inf[s]);
-    for (int j = 0; j < 5; ++j) tr.append_g1(pk.sig_comms[j], pk.sig_inf[j]);
-    for (uint64_t i = 0; i < pk.npub; ++i) tr.append_fr(pubs[i]);
-}
-
+// One proof on the per-proof path.  Host rounds: plonk_rounds.hpp, shared
+// with the cohort prover and the verifier.
 static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wires,
                             const Fr* pubs, uint64_t seed, uint64_t* out_proof,
                             uint64_t* out_link_hint) {
@@ -2102,18 +1949,17 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
     const uint32_t m = (uint32_t)(8 * n);
     if (prove_scratch_ensure(n) != RNG_OK) return RNG_ERR_HIP;
     ProveScratch* sc = tls_prove_scratch.get();
-    HostDrbg drbg(seed);
-    HostTranscript tr;
-    h_transcript_init(tr, pk, pubs);
+    ProofState st(pk, pubs, seed);
     Fr w = h_fr_root_of_unity((uint32_t)n);
-
-    G1Aff comms[13];
-    bool comm_inf[13] = {false};
+    G1Aff cbuf[5];  // one round's commitments, before the state takes them
+    bool ibuf[5];
 
     // --- R1: wire polys ---
-    std::vector<Fr> wpoly[5];
-    const bool z_dev = z_device_single() && n <= PERM_MAX_N;
-    const bool lagrange = r1_lagrange_single();
+    std::vector<Fr>* wpoly = st.wpoly;
+    const bool z_dev =
+        ProverEnv::on(prover_env().z_device, Z_DEVICE_DEFAULT_SINGLE) && n <= PERM_MAX_N;
+    const bool lagrange =
+        ProverEnv::on(prover_env().r1_lagrange, R1_LAGRANGE_DEFAULT_SINGLE);
     if (z_dev || lagrange) {
         // the wire evaluations go up once and stay in w_coset (free until
         // R3) for the device grand product and the Lagrange commit; the
@@ -2128,11 +1974,8 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
     } else if (ifft_columns(ctx, wires, n, 5, wpoly) != RNG_OK) {
         return RNG_ERR_HIP;
     }
-    Fr blind[10];
     for (int j = 0; j < 5; ++j) {
-        Fr b0 = drbg.next(), b1 = drbg.next();
-        blind[2 * j] = b0;
-        blind[2 * j + 1] = b1;
+        const Fr b0 = st.blind[BLIND_WIRES + 2 * j], b1 = st.blind[BLIND_WIRES + 2 * j + 1];
         wpoly[j].resize(n + 2, Fr::zero());
         wpoly[j][0] = wpoly[j][0].sub(b0);
         wpoly[j][1] = wpoly[j][1].sub(b1);
@@ -2144,69 +1987,63 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
         if (lagrange) {
             // commit the evaluations (still in w_coset) and the blinders
             // against the Lagrange bases: same group elements
-            HIP_CHECK(hipMemcpyAsync(sc->stage, blind, sizeof(blind), hipMemcpyHostToDevice,
-                                     RNG_STREAM));
+            HIP_CHECK(hipMemcpyAsync(sc->stage, st.blind + BLIND_WIRES, 10 * sizeof(Fr),
+                                     hipMemcpyHostToDevice, RNG_STREAM));
             uint64_t lt = 5 * (n + 2);
             hipLaunchKernelGGL(k_lagrange_scalars, dim3((uint32_t)((lt + 255) / 256)),
                                dim3(256), 0, RNG_STREAM, (const Fr*)sc->w_coset,
                                (const Fr*)sc->stage, (uint32_t)n, lt, sc->canon);
             HIP_CHECK(hipGetLastError());
-            crc = commit_lagrange_canon(ctx, n, sc->canon, 5, comms, comm_inf);
+            crc = commit_lagrange_canon(ctx, n, sc->canon, 5, cbuf, ibuf);
         }
         if (crc == MSM_LAGRANGE_UNUSABLE) {  // coefficient path
             const std::vector<Fr>* ps[5] = {&wpoly[0], &wpoly[1], &wpoly[2], &wpoly[3],
                                             &wpoly[4]};
-            crc = commit_dev_batch(ctx, ps, 5, comms, comm_inf);
+            crc = commit_dev_batch(ctx, ps, 5, cbuf, ibuf);
         }
         if (crc != RNG_OK) return RNG_ERR_HIP;
     }
-    for (int j = 0; j < 5; ++j) tr.append_g1(comms[j], comm_inf[j]);
-    if (out_link_hint) {
-        // hint = wire-0 polynomial (n+2 coeffs, Montgomery) + its commitment
-        memcpy(out_link_hint, wpoly[0].data(), (n + 2) * sizeof(Fr));
-        uint64_t* c = out_link_hint + 4 * (n + 2);
-        memcpy(c, comms[0].x.l, 32);
-        memcpy(c + 4, comms[0].y.l, 32);
-        c[8] = comm_inf[0] ? 1 : 0;
-    }
-    Fr beta = tr.challenge();
-    Fr gamma = tr.challenge();
+    st.take_comms(COMM_WIRES, 5, cbuf, ibuf);
+    if (out_link_hint) st.write_link_hint(out_link_hint);
+    st.beta = st.tr.challenge();
+    st.gamma = st.tr.challenge();
 
     // --- R2: grand product ---
-    std::vector<Fr> zpoly[1];
+    std::vector<Fr>& zpoly = st.zpoly;
     if (z_dev) {
         // device stage: terms/scans in q_buf, z evaluations in z_coset, and
         // straight into the inverse NTT; only the n coefficients come back
-        const Fr bg[2] = {beta, gamma};
+        const Fr bg[2] = {st.beta, st.gamma};
         int rc = perm_product_dev(sc->w_coset, pk.sig_evals_dev, pk.wpow_dev, pk.k, bg, n,
                                   1, sc->q_buf, sc->z_coset);
         if (rc != RNG_OK) return rc;
-        if (ifft_columns_dev(ctx, sc->z_coset, sc->tmp, n, 1, zpoly) != RNG_OK)
+        if (ifft_columns_dev(ctx, sc->z_coset, sc->tmp, n, 1, &zpoly) != RNG_OK)
             return RNG_ERR_HIP;
     } else {
         std::vector<Fr> zevals(n);
-        perm_product_host(pk, w, wires, beta, gamma, zevals.data());
-        if (ifft_columns(ctx, zevals.data(), n, 1, zpoly) != RNG_OK) return RNG_ERR_HIP;
+        perm_product_host(pk, w, wires, st.beta, st.gamma, zevals.data());
+        if (ifft_columns(ctx, zevals.data(), n, 1, &zpoly) != RNG_OK) return RNG_ERR_HIP;
     }
     {
-        Fr b2 = drbg.next(), b3 = drbg.next(), b4 = drbg.next();
-        zpoly[0].resize(n + 3, Fr::zero());
-        zpoly[0][0] = zpoly[0][0].sub(b4);
-        zpoly[0][1] = zpoly[0][1].sub(b3);
-        zpoly[0][2] = zpoly[0][2].sub(b2);
-        zpoly[0][n] = zpoly[0][n].add(b4);
-        zpoly[0][n + 1] = zpoly[0][n + 1].add(b3);
-        zpoly[0][n + 2] = zpoly[0][n + 2].add(b2);
+        const Fr b2 = st.blind[BLIND_Z], b3 = st.blind[BLIND_Z + 1],
+                 b4 = st.blind[BLIND_Z + 2];
+        zpoly.resize(n + 3, Fr::zero());
+        zpoly[0] = zpoly[0].sub(b4);
+        zpoly[1] = zpoly[1].sub(b3);
+        zpoly[2] = zpoly[2].sub(b2);
+        zpoly[n] = zpoly[n].add(b4);
+        zpoly[n + 1] = zpoly[n + 1].add(b3);
+        zpoly[n + 2] = zpoly[n + 2].add(b2);
     }
-    if (commit_dev(ctx, zpoly[0], &comms[5], &comm_inf[5]) != RNG_OK) return RNG_ERR_HIP;
-    tr.append_g1(comms[5], comm_inf[5]);
-    Fr alpha = tr.challenge();
+    if (commit_dev(ctx, zpoly, cbuf, ibuf) != RNG_OK) return RNG_ERR_HIP;
+    st.take_comms(COMM_Z, 1, cbuf, ibuf);
+    st.alpha = st.tr.challenge();
 
     // --- R3: quotient on the 8n coset (GPU) ---
     for (int j = 0; j < 5; ++j)
         if (coset_of_coeffs(ctx, wpoly[j], sc->w_coset + (size_t)j * m, m) != RNG_OK)
             return RNG_ERR_HIP;
-    if (coset_of_coeffs(ctx, zpoly[0], sc->z_coset, m) != RNG_OK) return RNG_ERR_HIP;
+    if (coset_of_coeffs(ctx, zpoly, sc->z_coset, m) != RNG_OK) return RNG_ERR_HIP;
     {
         std::vector<Fr> pie(n, Fr::zero());
         for (uint64_t i = 0; i < pk.npub; ++i) pie[i] = pubs[i];
@@ -2215,25 +2052,8 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
         if (coset_of_coeffs(ctx, picoef[0], sc->pi_coset, m) != RNG_OK)
             return RNG_ERR_HIP;
     }
-    QuotChal ch;
-    ch.beta = beta;
-    ch.gamma = gamma;
-    ch.alpha = alpha;
-    ch.alpha2 = alpha.sqr();
-    for (int j = 0; j < 5; ++j) ch.k[j] = pk.k[j];
-    {
-        Fr g = Fr::from_u64(FR_GENERATOR);
-        Fr gn = g.pow_u64(n);
-        Fr w8 = h_fr_root_of_unity(m).pow_u64(n);
-        std::vector<Fr> zh(8);
-        Fr cur = gn;
-        for (int t = 0; t < 8; ++t) {
-            zh[t] = cur.sub(Fr::one());
-            cur = cur.mul(w8);
-        }
-        zh = hbatch_inverse(zh);
-        for (int t = 0; t < 8; ++t) ch.zh_inv[t] = zh[t];
-    }
+    QuotChal ch = quot_chal_fixed(pk);
+    quot_chal_set(ch, st);
     NttPlan* mp = get_plan(ctx, m, 1);
     if (!mp || ensure_coset_tables(ctx, mp) != RNG_OK) return RNG_ERR_HIP;
     {
@@ -2248,13 +2068,13 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
     HIP_CHECK(hipMemcpyAsync(quot.data(), sc->tmp, quot.size() * sizeof(Fr),
                              hipMemcpyDeviceToHost, RNG_STREAM));
     HIP_CHECK(hipStreamSynchronize(RNG_STREAM));
-    std::vector<Fr> quot_chunks[5];
+    std::vector<Fr>* quot_chunks = st.quot_chunks;
     {
         Fr prev = Fr::zero();
         for (int i = 0; i < 5; ++i) {
             quot_chunks[i].assign(quot.begin() + (size_t)i * (n + 2),
                                   quot.begin() + (size_t)(i + 1) * (n + 2));
-            Fr bnext = (i < 4) ? drbg.next() : Fr::zero();
+            Fr bnext = (i < 4) ? st.blind[BLIND_CHUNKS + i] : Fr::zero();
             quot_chunks[i][0] = quot_chunks[i][0].sub(prev);
             if (i < 4) {
                 quot_chunks[i].resize(n + 3, Fr::zero());
@@ -2264,89 +2084,20 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
         }
         const std::vector<Fr>* ps[5] = {&quot_chunks[0], &quot_chunks[1], &quot_chunks[2],
                                         &quot_chunks[3], &quot_chunks[4]};
-        if (commit_dev_batch(ctx, ps, 5, comms + 6, comm_inf + 6) != RNG_OK)
-            return RNG_ERR_HIP;
-        for (int i = 0; i < 5; ++i) tr.append_g1(comms[6 + i], comm_inf[6 + i]);
+        if (commit_dev_batch(ctx, ps, 5, cbuf, ibuf) != RNG_OK) return RNG_ERR_HIP;
+        st.take_comms(COMM_CHUNKS, 5, cbuf, ibuf);
     }
-    Fr zeta = tr.challenge();
+    st.zeta = st.tr.challenge();
 
-    // --- R4: evaluations ---
-    Fr wire_evals[5], sigma_evals[4], z_shift_eval;
-    for (int j = 0; j < 5; ++j) {
-        wire_evals[j] = hpoly_eval(wpoly[j], zeta);
-        tr.append_fr(wire_evals[j]);
-    }
-    for (int j = 0; j < 4; ++j) {
-        sigma_evals[j] = hpoly_eval(pk.sigp[j], zeta);
-        tr.append_fr(sigma_evals[j]);
-    }
-    z_shift_eval = hpoly_eval(zpoly[0], zeta.mul(w));
-    tr.append_fr(z_shift_eval);
-    Fr v = tr.challenge();
-
-    // --- R5: linearization + openings ---
-    Fr zeta_n = zeta.pow_u64(n);
-    Fr zh_zeta = zeta_n.sub(Fr::one());
-    Fr l1_zeta = zh_zeta.mul(Fr::from_u64(n).mul(zeta.sub(Fr::one())).inverse());
-    auto p5 = [](const Fr& x) {
-        Fr x2 = x.sqr();
-        return x2.sqr().mul(x);
-    };
-    const Fr* wb = wire_evals;
-    std::vector<Fr> D;
-    hpoly_add_scaled(D, pk.selq[11], Fr::one());
-    for (int j = 0; j < 4; ++j) hpoly_add_scaled(D, pk.selq[j], wb[j]);
-    hpoly_add_scaled(D, pk.selq[4], wb[0].mul(wb[1]));
-    hpoly_add_scaled(D, pk.selq[5], wb[2].mul(wb[3]));
-    for (int j = 0; j < 4; ++j) hpoly_add_scaled(D, pk.selq[6 + j], p5(wb[j]));
-    hpoly_add_scaled(D, pk.selq[12],
-                     wb[0].mul(wb[1]).mul(wb[2]).mul(wb[3]).mul(wb[4]));
-    hpoly_add_scaled(D, pk.selq[10], wb[4].neg());
-    Fr fbar = Fr::one(), Bbar = Fr::one();
-    for (int j = 0; j < 5; ++j)
-        fbar = fbar.mul(wb[j].add(beta.mul(pk.k[j]).mul(zeta)).add(gamma));
-    for (int j = 0; j < 4; ++j)
-        Bbar = Bbar.mul(wb[j].add(beta.mul(sigma_evals[j])).add(gamma));
-    hpoly_add_scaled(D, zpoly[0], alpha.mul(fbar).add(alpha.sqr().mul(l1_zeta)));
-    hpoly_add_scaled(D, pk.sigp[4], alpha.mul(beta).mul(z_shift_eval).mul(Bbar).neg());
-    {
-        Fr zpow = zh_zeta.neg();
-        Fr step = zeta.pow_u64(n + 2);
-        for (int i = 0; i < 5; ++i) {
-            hpoly_add_scaled(D, quot_chunks[i], zpow);
-            zpow = zpow.mul(step);
-        }
-    }
-    std::vector<Fr> C = D;
-    Fr vp = Fr::one();
-    for (int j = 0; j < 5; ++j) {
-        vp = vp.mul(v);
-        hpoly_add_scaled(C, wpoly[j], vp);
-    }
-    for (int j = 0; j < 4; ++j) {
-        vp = vp.mul(v);
-        hpoly_add_scaled(C, pk.sigp[j], vp);
-    }
-    std::vector<Fr> Wz = hpoly_div_linear(C, zeta);
-    std::vector<Fr> Wzw = hpoly_div_linear(zpoly[0], zeta.mul(w));
+    // --- R4 + R5: evaluations, linearization, openings (host) ---
+    std::vector<Fr> Wz, Wzw;
+    rounds_4_5(pk, w, st, Wz, Wzw);
     {
         const std::vector<Fr>* ps[2] = {&Wz, &Wzw};
-        if (commit_dev_batch(ctx, ps, 2, comms + 11, comm_inf + 11) != RNG_OK)
-            return RNG_ERR_HIP;
+        if (commit_dev_batch(ctx, ps, 2, cbuf, ibuf) != RNG_OK) return RNG_ERR_HIP;
     }
-    tr.append_g1(comms[11], comm_inf[11]);
-    tr.append_g1(comms[12], comm_inf[12]);
-
-    // --- serialize (layout: include/rng_prover.h) ---
-    for (int i = 0; i < 13; ++i) {
-        memcpy(out_proof + 9 * i, comms[i].x.l, 32);
-        memcpy(out_proof + 9 * i + 4, comms[i].y.l, 32);
-        out_proof[9 * i + 8] = comm_inf[i] ? 1 : 0;
-    }
-    uint64_t* e = out_proof + 117;
-    for (int i = 0; i < 5; ++i) memcpy(e + 4 * i, wire_evals[i].l, 32);
-    for (int i = 0; i < 4; ++i) memcpy(e + 20 + 4 * i, sigma_evals[i].l, 32);
-    memcpy(e + 36, z_shift_eval.l, 32);
+    st.take_comms(COMM_WZ, 2, cbuf, ibuf);
+    st.serialize(out_proof);
     return RNG_OK;
 }
 
@@ -2788,1669 +2539,7 @@ int rng_msm_g1(RngCtx* ctx, const uint64_t* bases, const uint64_t* scalars, uint
     return rc;
 }
 
-// ---- circuit construction (arithmetization front-end) ----
-// The tables handle wraps rng::CircuitTables; getters copy flat arrays out
-// so tests (and the oracle prover) consume identical inputs.
-
-void* rng_testcirc_build(uint64_t seed, uint64_t scale) {
-    try {
-        PlonkCircuit cs;
-        build_mixed_circuit(cs, seed, scale);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_testcirc_build: %s\n", why.c_str());
-            return nullptr;
-        }
-        auto* t = new CircuitTables(cs.finalize());
-        return t;
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_testcirc_build: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// `Valid Balance Create` circuit builder (zk_circuits/valid_balance_create.rs)
-// with fixed-seed witness/statement; returns finalized tables.
-void* rng_circ_build_vbc(uint64_t seed) {
-    try {
-        VbcWitness w;
-        VbcStatement st;
-        vbc_build_witness_statement(seed, w, st);
-        PlonkCircuit cs;
-        vbc_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_vbc: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_vbc: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// `Intent And Balance Private Settlement` circuit builder (the VALID MATCH
-// MPC successor; zk_circuits/settlement/intent_and_balance_private_settlement.rs)
-void* rng_circ_build_settlement(uint64_t seed) {
-    try {
-        SettlementWitness w;
-        SettlementStatement st;
-        settlement_build_witness_statement(seed, w, st);
-        PlonkCircuit cs;
-        settlement_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_settlement: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_settlement: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// --- validity <-> settlement proof bundle builders ---
-// (zk_circuits/validity_proofs/intent_and_balance.rs; the validity circuit's
-//  two link groups are placed at the SETTLEMENT circuit's layout, :316-341.)
-
-// settlement circuit whose pre-update shares come from the two validity
-// witnesses of the same seed (the consistent production bundle)
-void* rng_circ_build_settlement_bundle(uint64_t seed) {
-    try {
-        ValidityBundle b;
-        validity_bundle_build(seed, b);
-        PlonkCircuit cs;
-        settlement_apply_constraints(cs, b.sw, b.sst);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_settlement_bundle: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_settlement_bundle: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT AND BALANCE VALIDITY circuit for party 0 or 1 of the seed's bundle
-void* rng_circ_build_validity(uint64_t seed, uint64_t party) {
-    try {
-        ValidityBundle b;
-        validity_bundle_build(seed, b);
-        // read the settlement circuit's link-group placement (inherited layout)
-        uint64_t align = 0;
-        int64_t off[2] = {0, 0};
-        {
-            PlonkCircuit scs;
-            settlement_apply_constraints(scs, b.sw, b.sst);
-            CircuitTables stt = scs.finalize();
-            const char* names[2] = {"intent_and_balance_settlement_party0",
-                                    "intent_and_balance_settlement_party1"};
-            for (auto& g : stt.link_groups)
-                for (int i = 0; i < 2; ++i)
-                    if (g.id == names[i]) {
-                        align = g.alignment;
-                        off[i] = (int64_t)g.offset;
-                    }
-        }
-        int p = (int)(party & 1);
-        PlonkCircuit cs;
-        validity_apply_constraints(cs, b.vw[p], b.vst[p], (int)align, off[0], off[1]);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_validity: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_validity: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// OUTPUT BALANCE VALIDITY circuit for party 0 or 1 of the seed's bundle
-// (validity_proofs/output_balance.rs; links at the settlement's
-//  output_balance_settlement_party{0,1} layout)
-void* rng_circ_build_ob_validity(uint64_t seed, uint64_t party) {
-    try {
-        ValidityBundle b;
-        validity_bundle_build(seed, b);
-        uint64_t align = 0;
-        int64_t off[2] = {0, 0};
-        {
-            PlonkCircuit scs;
-            settlement_apply_constraints(scs, b.sw, b.sst);
-            CircuitTables stt = scs.finalize();
-            const char* names[2] = {"output_balance_settlement_party0",
-                                    "output_balance_settlement_party1"};
-            for (auto& g : stt.link_groups)
-                for (int i = 0; i < 2; ++i)
-                    if (g.id == names[i]) {
-                        align = g.alignment;
-                        off[i] = (int64_t)g.offset;
-                    }
-        }
-        int p = (int)(party & 1);
-        PlonkCircuit cs;
-        ob_validity_apply_constraints(cs, b.ow[p], b.ost[p], (int)align, off[0], off[1]);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_ob_validity: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_ob_validity: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT AND BALANCE PUBLIC SETTLEMENT circuit for party 0 of the seed's
-// bundle (settlement/intent_and_balance_public_settlement.rs); its two link
-// groups are placed at the private settlement's party-0 layout.
-void* rng_circ_build_public_settlement(uint64_t seed) {
-    try {
-        ValidityBundle b;
-        validity_bundle_build(seed, b);
-        uint64_t align = 0;
-        int64_t pg_off = 0, og_off = 0;
-        {
-            PlonkCircuit scs;
-            settlement_apply_constraints(scs, b.sw, b.sst);
-            CircuitTables stt = scs.finalize();
-            for (auto& g : stt.link_groups) {
-                if (g.id == "intent_and_balance_settlement_party0") {
-                    align = g.alignment;
-                    pg_off = (int64_t)g.offset;
-                }
-                if (g.id == "output_balance_settlement_party0") og_off = (int64_t)g.offset;
-            }
-        }
-        PubSettlementStatement st;
-        pub_settlement_statement_from_bundle(b, st);
-        PlonkCircuit cs;
-        pub_settlement_apply_constraints(cs, b.sw.p[0], st, (int)align, pg_off, og_off);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_public_settlement: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_public_settlement: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT ONLY PUBLIC SETTLEMENT circuit (intent_only_public_settlement.rs)
-void* rng_circ_build_io_settlement(uint64_t seed) {
-    try {
-        IoValidityWitness vw;
-        IoValidityStatement vs;
-        IoSettlementStatement ss;
-        io_bundle_build(seed, vw, vs, ss);
-        PlonkCircuit cs;
-        io_settlement_apply_constraints(cs, vw.intent, ss);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_io_settlement: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_io_settlement: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT ONLY VALIDITY circuit (validity_proofs/intent_only.rs); its link
-// group inherits the INTENT ONLY PUBLIC SETTLEMENT placement
-void* rng_circ_build_io_validity(uint64_t seed) {
-    try {
-        IoValidityWitness vw;
-        IoValidityStatement vs;
-        IoSettlementStatement ss;
-        io_bundle_build(seed, vw, vs, ss);
-        uint64_t align = 0;
-        int64_t off = 0;
-        {
-            PlonkCircuit scs;
-            io_settlement_apply_constraints(scs, vw.intent, ss);
-            CircuitTables stt = scs.finalize();
-            for (auto& g : stt.link_groups)
-                if (g.id == "intent_only_settlement") {
-                    align = g.alignment;
-                    off = (int64_t)g.offset;
-                }
-        }
-        PlonkCircuit cs;
-        io_validity_apply_constraints(cs, vw, vs, (int)align, off);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_io_validity: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_io_validity: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT ONLY BOUNDED SETTLEMENT circuit (intent_only_bounded_settlement.rs)
-void* rng_circ_build_io_bounded_settlement(uint64_t seed) {
-    try {
-        IoValidityWitness vw;
-        IoValidityStatement vs;
-        IoSettlementStatement ss;
-        io_bundle_build(seed, vw, vs, ss);
-        uint64_t align = 0;
-        int64_t off = 0;
-        {
-            PlonkCircuit scs;
-            io_settlement_apply_constraints(scs, vw.intent, ss);
-            CircuitTables stt = scs.finalize();
-            for (auto& g : stt.link_groups)
-                if (g.id == "intent_only_settlement") {
-                    align = g.alignment;
-                    off = (int64_t)g.offset;
-                }
-        }
-        IoBoundedStatement st;
-        io_bounded_statement_build(seed, vw, ss, st);
-        PlonkCircuit cs;
-        io_bounded_apply_constraints(cs, vw.intent, st, (int)align, off);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_io_bounded_settlement: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_io_bounded_settlement: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT AND BALANCE BOUNDED SETTLEMENT circuit
-// (intent_and_balance_bounded_settlement.rs; party-0 groups at the private
-//  settlement layout)
-void* rng_circ_build_ib_bounded_settlement(uint64_t seed) {
-    try {
-        ValidityBundle b;
-        validity_bundle_build(seed, b);
-        uint64_t align = 0;
-        int64_t pg_off = 0, og_off = 0;
-        {
-            PlonkCircuit scs;
-            settlement_apply_constraints(scs, b.sw, b.sst);
-            CircuitTables stt = scs.finalize();
-            for (auto& g : stt.link_groups) {
-                if (g.id == "intent_and_balance_settlement_party0") {
-                    align = g.alignment;
-                    pg_off = (int64_t)g.offset;
-                }
-                if (g.id == "output_balance_settlement_party0") og_off = (int64_t)g.offset;
-            }
-        }
-        IbBoundedStatement st;
-        ib_bounded_statement_from_bundle(b, st);
-        PlonkCircuit cs;
-        ib_bounded_apply_constraints(cs, b.sw.p[0], st, (int)align, pg_off, og_off);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_ib_bounded_settlement: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_ib_bounded_settlement: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT ONLY FIRST FILL VALIDITY (validity_proofs/intent_only_first_fill.rs);
-// shares the seed's intent with rng_circ_build_io_settlement so the proofs link
-void* rng_circ_build_ioff(uint64_t seed) {
-    try {
-        IoffWitness w;
-        IoffStatement st;
-        ioff_build(seed, w, st);
-        uint64_t align = 0;
-        int64_t off = 0;
-        {
-            IoValidityWitness vw;
-            IoValidityStatement vs;
-            IoSettlementStatement ss;
-            io_bundle_build(seed, vw, vs, ss);
-            PlonkCircuit scs;
-            io_settlement_apply_constraints(scs, vw.intent, ss);
-            CircuitTables stt = scs.finalize();
-            for (auto& g : stt.link_groups)
-                if (g.id == "intent_only_settlement") {
-                    align = g.alignment;
-                    off = (int64_t)g.offset;
-                }
-        }
-        PlonkCircuit cs;
-        ioff_apply_constraints(cs, w, st, (int)align, off);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_ioff: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_ioff: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// Baby Jubjub native test shims (tests/test_jubjub.py pins the C++ curve
-// arithmetic + Schnorr/ElGamal against an independent pure-Python bignum
-// implementation).  Scalars: 4 u64 plain LE; points: x,y Montgomery Fr.
-int rng_jj_mul(const uint64_t* scalar4, const uint64_t* px4, const uint64_t* py4,
-               uint64_t* out_xy8) {
-    JjPoint p;
-    memcpy(p.x.l, px4, 32);
-    memcpy(p.y.l, py4, 32);
-    if (!jj_on_curve(p) && !(p.x.is_zero())) return RNG_ERR_BAD_ARG;
-    JjPoint r = jj_mul(scalar4, p);
-    memcpy(out_xy8, r.x.l, 32);
-    memcpy(out_xy8 + 4, r.y.l, 32);
-    return RNG_OK;
-}
-
-void rng_jj_base(uint64_t* out_xy8) {
-    JjPoint b = jj_base();
-    memcpy(out_xy8, b.x.l, 32);
-    memcpy(out_xy8 + 4, b.y.l, 32);
-}
-
-// sign/verify round trip: sk, nonce k as plain scalars; msg = n Fr
-// (Montgomery); out = s (4 u64 plain), R (8 u64 Montgomery xy)
-int rng_jj_sign(const uint64_t* sk4, const uint64_t* k4, const uint64_t* msg,
-                uint64_t n, uint64_t* out_s4, uint64_t* out_r8) {
-    JjScalar sk, k;
-    memcpy(sk.v, sk4, 32);
-    memcpy(k.v, k4, 32);
-    JjSignature sig = jj_sign(sk, k, (const Fr*)msg, n);
-    memcpy(out_s4, sig.s.v, 32);
-    memcpy(out_r8, sig.R.x.l, 32);
-    memcpy(out_r8 + 4, sig.R.y.l, 32);
-    return RNG_OK;
-}
-
-int rng_jj_verify(const uint64_t* vk8, const uint64_t* s4, const uint64_t* r8,
-                  const uint64_t* msg, uint64_t n) {
-    JjPoint vk;
-    memcpy(vk.x.l, vk8, 32);
-    memcpy(vk.y.l, vk8 + 4, 32);
-    JjSignature sig;
-    memcpy(sig.s.v, s4, 32);
-    memcpy(sig.R.x.l, r8, 32);
-    memcpy(sig.R.y.l, r8 + 4, 32);
-    return jj_verify(vk, sig, (const Fr*)msg, n) ? 1 : 0;
-}
-
-int rng_jj_elgamal(const uint64_t* pk8, const uint64_t* k4, const uint64_t* msg12,
-                   uint64_t* out_eph8, uint64_t* out_c12) {
-    JjPoint pk;
-    memcpy(pk.x.l, pk8, 32);
-    memcpy(pk.y.l, pk8 + 4, 32);
-    JjScalar k;
-    memcpy(k.v, k4, 32);
-    JjCiphertext<3> ct = jj_elgamal_encrypt<3>(pk, k, (const Fr*)msg12);
-    memcpy(out_eph8, ct.ephemeral_key.x.l, 32);
-    memcpy(out_eph8 + 4, ct.ephemeral_key.y.l, 32);
-    memcpy(out_c12, ct.ciphertext, 96);
-    return RNG_OK;
-}
-
-// embedded-curve gadget self-tests (Schnorr / ElGamal over Baby Jubjub):
-// native-sign -> in-circuit verify; returns the finalized tables or null if
-// the circuit is unsatisfied (tamper != 0 flips a signature/ciphertext bit
-// and MUST yield null)
-void* rng_testcirc_schnorr(uint64_t seed, int tamper) {
-    try {
-        Lcg rng(seed);
-        auto sc = [&]() {
-            JjScalar s{{rng.next() | (rng.next() << 52),
-                        rng.next() | (rng.next() << 52),
-                        rng.next() | (rng.next() << 52), rng.next() & 0x3FFFFFFFFFFull}};
-            return s;  // < 2^250 < l
-        };
-        JjScalar sk = sc(), k = sc();
-        Fr msg[3] = {rng.fr(), rng.fr(), rng.fr()};
-        JjPoint vk = jj_pubkey(sk);
-        JjSignature sig = jj_sign(sk, k, msg, 3);
-        if (!jj_verify(vk, sig, msg, 3)) {
-            fprintf(stderr, "rng_testcirc_schnorr: native verify failed\n");
-            return nullptr;
-        }
-        if (tamper) sig.s.v[0] ^= 1;
-        PlonkCircuit cs;
-        JjPointVars vkv{cs.create_variable(vk.x), cs.create_variable(vk.y)};
-        JjPointVars Rv{cs.create_variable(sig.R.x), cs.create_variable(sig.R.y)};
-        Fr s_fr = Fr::from_canonical(sig.s.v);
-        Var sv = cs.create_variable(s_fr);
-        std::vector<Var> mv;
-        for (int i = 0; i < 3; ++i) mv.push_back(cs.create_variable(msg[i]));
-        schnorr_verify_gadget(cs, vkv, Rv, sv, mv);
-        std::string why;
-        if (!cs.check_satisfied(&why)) return nullptr;
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_testcirc_schnorr: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-void* rng_testcirc_elgamal(uint64_t seed, int tamper) {
-    try {
-        Lcg rng(seed);
-        JjScalar dk{{rng.next() | (rng.next() << 52), rng.next() | (rng.next() << 52),
-                     rng.next() | (rng.next() << 52), rng.next() & 0x3FFFFFFFFFFull}};
-        JjScalar k{{rng.next() | (rng.next() << 52), rng.next() | (rng.next() << 52),
-                    rng.next() | (rng.next() << 52), rng.next() & 0x3FFFFFFFFFFull}};
-        JjPoint pk = jj_pubkey(dk);
-        Fr msg[3] = {rng.fr(), rng.fr(), rng.fr()};
-        JjCiphertext<3> ct = jj_elgamal_encrypt<3>(pk, k, msg);
-        if (tamper) ct.ciphertext[1] = ct.ciphertext[1].add(Fr::one());
-        PlonkCircuit cs;
-        JjPointVars pkv{cs.create_variable(pk.x), cs.create_variable(pk.y)};
-        Var kv = cs.create_variable(Fr::from_canonical(k.v));
-        std::vector<Var> mv;
-        for (int i = 0; i < 3; ++i) mv.push_back(cs.create_variable(msg[i]));
-        JjPointVars eph;
-        std::vector<Var> cipher;
-        elgamal_encrypt_gadget(cs, pkv, kv, mv, eph, cipher);
-        // constrain against the native ciphertext (the statement shape)
-        Var ex = cs.create_public_variable(ct.ephemeral_key.x);
-        Var ey = cs.create_public_variable(ct.ephemeral_key.y);
-        cs.enforce_equal(eph.x, ex);
-        cs.enforce_equal(eph.y, ey);
-        for (int i = 0; i < 3; ++i) {
-            Var ci = cs.create_public_variable(ct.ciphertext[i]);
-            cs.enforce_equal(cipher[i], ci);
-        }
-        std::string why;
-        if (!cs.check_satisfied(&why)) return nullptr;
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_testcirc_elgamal: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// ---- fee circuits (zk_circuits/fees/) ----
-
-// VALID NOTE REDEMPTION (fees/valid_note_redemption.rs)
-void* rng_circ_build_note_redemption(uint64_t seed) {
-    try {
-        NoteRedemptionWitness w;
-        NoteRedemptionStatement st;
-        note_redemption_build(seed, w, st);
-        PlonkCircuit cs;
-        note_redemption_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_note_redemption: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_note_redemption: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// shared fee-payment builder; variant: 0 = public relayer, 1 = public
-// protocol, 2 = private relayer (fees/valid_{public,private}_{relayer,
-// protocol}_fee_payment.rs; private protocol needs in-circuit ElGamal and
-// lands with the embedded-curve gadget)
-static void* build_fee_payment(uint64_t seed, int variant, const char* name) {
-    try {
-        VdWitness w;
-        FeePaymentStatement st;
-        Note note;
-        int field = (variant == 1) ? 6 : 5;
-        fee_payment_build(seed, field, w, st, note);
-        std::vector<Fr> ss = {st.merkle_root, st.old_balance_nullifier,
-                              st.new_balance_commitment, st.recovery_id,
-                              st.new_fee_balance_share};
-        int note_mode = (variant == 2) ? 1 : 0;
-        if (note_mode == 0) {
-            auto nv = note.to_scalars();
-            ss.insert(ss.end(), nv.begin(), nv.end());
-        } else {
-            ss.push_back(note.receiver);
-            ss.push_back(native_note_commitment(note));
-        }
-        PlonkCircuit cs;
-        fee_payment_apply_constraints(cs, w, note.blinder, field, note_mode,
-                                      /*check_receiver=*/variant != 1, ss);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "%s: %s\n", name, why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "%s: %s\n", name, e.what());
-        return nullptr;
-    }
-}
-
-void* rng_circ_build_fee_public_relayer(uint64_t seed) {
-    return build_fee_payment(seed, 0, "rng_circ_build_fee_public_relayer");
-}
-void* rng_circ_build_fee_public_protocol(uint64_t seed) {
-    return build_fee_payment(seed, 1, "rng_circ_build_fee_public_protocol");
-}
-void* rng_circ_build_fee_private_relayer(uint64_t seed) {
-    return build_fee_payment(seed, 2, "rng_circ_build_fee_private_relayer");
-}
-
-// VALID PRIVATE PROTOCOL FEE PAYMENT (in-circuit ElGamal note encryption)
-void* rng_circ_build_fee_private_protocol(uint64_t seed) {
-    try {
-        VdWitness w;
-        FeePaymentStatement st;
-        Note note;
-        fee_payment_build(seed, 6, w, st, note);
-        Lcg rng(seed ^ 0xE161A3A1E161A3A1ull);
-        // protocol receiver comes from the statement, not the balance
-        u64 al[4] = {rng.next() | (rng.next() << 53), rng.next() | (rng.next() << 53),
-                     rng.next() & 0xFFFFFFFF, 0};
-        note.receiver = Fr::from_canonical(al);
-        JjScalar dk = jj_random_scalar(rng);
-        JjScalar k = jj_random_scalar(rng);
-        JjPoint pk = jj_pubkey(dk);
-        Fr plain[3] = {note.mint, note.amount, note.blinder};
-        JjCiphertext<3> ct = jj_elgamal_encrypt<3>(pk, k, plain);
-        std::vector<Fr> ss = {st.merkle_root, st.old_balance_nullifier,
-                              st.new_balance_commitment, st.recovery_id,
-                              st.new_fee_balance_share, note.receiver,
-                              native_note_commitment(note), ct.ephemeral_key.x,
-                              ct.ephemeral_key.y, ct.ciphertext[0], ct.ciphertext[1],
-                              ct.ciphertext[2], pk.x, pk.y};
-        PlonkCircuit cs;
-        fee_private_protocol_apply_constraints(cs, w, note.blinder,
-                                               Fr::from_canonical(k.v), ss);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_fee_private_protocol: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_fee_private_protocol: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// INTENT AND BALANCE FIRST FILL VALIDITY for bundle party 0/1
-// (validity_proofs/intent_and_balance_first_fill.rs; links at the private
-//  settlement's party layouts)
-void* rng_circ_build_ff_validity(uint64_t seed, uint64_t party) {
-    try {
-        ValidityBundle b;
-        validity_bundle_build(seed, b);
-        uint64_t align = 0;
-        int64_t off[2] = {0, 0};
-        {
-            PlonkCircuit scs;
-            settlement_apply_constraints(scs, b.sw, b.sst);
-            CircuitTables stt = scs.finalize();
-            const char* names[2] = {"intent_and_balance_settlement_party0",
-                                    "intent_and_balance_settlement_party1"};
-            for (auto& g : stt.link_groups)
-                for (int i = 0; i < 2; ++i)
-                    if (g.id == names[i]) {
-                        align = g.alignment;
-                        off[i] = (int64_t)g.offset;
-                    }
-        }
-        int p = (int)(party & 1);
-        FfWitness w;
-        FfStatement st;
-        ff_build(b, p, seed, w, st);
-        PlonkCircuit cs;
-        ff_apply_constraints(cs, w, st, (int)align, off[0], off[1]);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_ff_validity: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_ff_validity: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// NEW OUTPUT BALANCE VALIDITY (validity_proofs/new_output_balance.rs; links
-// at the settlement's output-balance layouts)
-void* rng_circ_build_nob_validity(uint64_t seed) {
-    try {
-        NobWitness w;
-        NobStatement st;
-        nob_build(seed, w, st);
-        uint64_t align = 0;
-        int64_t off[2] = {0, 0};
-        {
-            ValidityBundle b;
-            validity_bundle_build(seed, b);
-            PlonkCircuit scs;
-            settlement_apply_constraints(scs, b.sw, b.sst);
-            CircuitTables stt = scs.finalize();
-            const char* names[2] = {"output_balance_settlement_party0",
-                                    "output_balance_settlement_party1"};
-            for (auto& g : stt.link_groups)
-                for (int i = 0; i < 2; ++i)
-                    if (g.id == names[i]) {
-                        align = g.alignment;
-                        off[i] = (int64_t)g.offset;
-                    }
-        }
-        PlonkCircuit cs;
-        nob_apply_constraints(cs, w, st, (int)align, off[0], off[1]);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_nob_validity: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_nob_validity: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// ---- link-group layouts of the placing circuits (computed once) ----
-// The settlement circuits PLACE the groups; validity circuits inherit them.
-// Layout depends only on circuit structure, so compute from a fixed seed.
-struct LinkLayouts {
-    uint64_t ib_align = 0;
-    int64_t pg0 = 0, og0 = 0, pg1 = 0, og1 = 0;  // private-settlement groups
-    uint64_t io_align = 0;
-    int64_t io_off = 0;  // intent-only settlement group
-};
-static const LinkLayouts& link_layouts() {
-    static LinkLayouts L;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        ValidityBundle b;
-        validity_bundle_build(42, b);
-        PlonkCircuit scs;
-        settlement_apply_constraints(scs, b.sw, b.sst);
-        CircuitTables t = scs.finalize();
-        for (auto& g : t.link_groups) {
-            if (g.id == "intent_and_balance_settlement_party0") {
-                L.ib_align = g.alignment;
-                L.pg0 = (int64_t)g.offset;
-            } else if (g.id == "intent_and_balance_settlement_party1") {
-                L.pg1 = (int64_t)g.offset;
-            } else if (g.id == "output_balance_settlement_party0") {
-                L.og0 = (int64_t)g.offset;
-            } else if (g.id == "output_balance_settlement_party1") {
-                L.og1 = (int64_t)g.offset;
-            }
-        }
-        IoValidityWitness vw;
-        IoValidityStatement vs;
-        IoSettlementStatement ss;
-        io_bundle_build(42, vw, vs, ss);
-        PlonkCircuit c2;
-        io_settlement_apply_constraints(c2, vw.intent, ss);
-        CircuitTables t2 = c2.finalize();
-        for (auto& g : t2.link_groups)
-            if (g.id == "intent_only_settlement") {
-                L.io_align = g.alignment;
-                L.io_off = (int64_t)g.offset;
-            }
-    });
-    return L;
-}
-
-// ---- witness/statement parsers (scalar cursor over the field orders the
-//      route bodies use; see rng_prover.h kind table) ----
-namespace {
-struct Rd {
-    const Fr* p;
-    Fr f() { return *p++; }
-    uint64_t u() {
-        u64 l[4];
-        (*p).to_canonical(l);
-        ++p;
-        return l[0];
-    }
-    void frs(Fr* dst, int n) {
-        for (int i = 0; i < n; ++i) dst[i] = f();
-    }
-    Csprng cs() {
-        Csprng c;
-        c.seed = f();
-        c.index = u();
-        return c;
-    }
-    Balance bal() {
-        Balance b;
-        Fr s[8];
-        frs(s, 8);
-        b.from_scalars(s);
-        return b;
-    }
-    Intent in() {
-        Intent i;
-        i.in_token = f();
-        i.out_token = f();
-        i.owner = f();
-        i.min_price_repr = f();
-        i.amount_in = f();
-        return i;
-    }
-    PostMatchShare pms() {
-        PostMatchShare s;
-        s.relayer_fee_balance = f();
-        s.protocol_fee_balance = f();
-        s.amount = f();
-        return s;
-    }
-    Obligation ob() {
-        Obligation o;
-        o.input_token = f();
-        o.output_token = f();
-        o.amount_in = f();
-        o.amount_out = f();
-        return o;
-    }
-    StateBalance sbal() {
-        StateBalance s;
-        s.recovery = cs();
-        s.share = cs();
-        s.inner = bal();
-        frs(s.public_share, 8);
-        return s;
-    }
-    StateIntent sint() {
-        StateIntent s;
-        s.recovery = cs();
-        s.share = cs();
-        s.inner = in();
-        frs(s.public_share, 5);
-        return s;
-    }
-    void opening(Fr* elems, bool* idx) {
-        frs(elems, MERKLE_HEIGHT);
-        for (int i = 0; i < MERKLE_HEIGHT; ++i) idx[i] = u() != 0;
-    }
-    JjSignature sig() {
-        JjSignature s;
-        Fr sf = f();
-        sf.to_canonical(s.s.v);
-        s.R.x = f();
-        s.R.y = f();
-        return s;
-    }
-    Note note() {
-        Note n;
-        n.mint = f();
-        n.amount = f();
-        n.receiver = f();
-        n.blinder = f();
-        return n;
-    }
-    SettlementParty party_no_ob() {  // public/bounded settlement witness (28)
-        SettlementParty p;
-        p.intent = in();
-        p.pre_amount_share = f();
-        p.input_balance = bal();
-        p.pre_in_shares = pms();
-        p.output_balance = bal();
-        p.pre_out_shares = pms();
-        return p;
-    }
-};
-}  // namespace
-
-namespace {
-struct Wt {  // writer mirroring Rd
-    Fr* p;
-    void f(const Fr& v) { *p++ = v; }
-    void u(uint64_t x) { *p++ = Fr::from_u64(x); }
-    void frs(const Fr* src, int n) {
-        for (int i = 0; i < n; ++i) f(src[i]);
-    }
-    void cs(const Csprng& c) {
-        f(c.seed);
-        u(c.index);
-    }
-    void bal(const Balance& b) {
-        for (auto& s : b.to_scalars()) f(s);
-    }
-    void in(const Intent& i) {
-        for (auto& s : i.to_scalars()) f(s);
-    }
-    void pms(const PostMatchShare& s_) {
-        for (auto& s : s_.to_scalars()) f(s);
-    }
-    void sbal(const StateBalance& s_) {
-        for (auto& s : s_.to_scalars()) f(s);
-    }
-    void sint(const StateIntent& s_) {
-        for (auto& s : s_.to_scalars()) f(s);
-    }
-    void opening(const Fr* elems, const bool* idx) {
-        frs(elems, MERKLE_HEIGHT);
-        for (int i = 0; i < MERKLE_HEIGHT; ++i) u(idx[i] ? 1 : 0);
-    }
-    void sig(const JjSignature& s_) {
-        f(Fr::from_canonical(s_.s.v));
-        f(s_.R.x);
-        f(s_.R.y);
-    }
-    void st(const std::vector<Fr>& v) {
-        for (auto& s : v) f(s);
-    }
-};
-}  // namespace
-
-// per-kind witness/statement scalar counts (the route body sizes)
-int rng_ws_sizes(int kind, uint64_t* out_nw, uint64_t* out_ns) {
-    struct {
-        int k, nw, ns;
-    } T[] = {{1, 40, 8},  {2, 40, 8},  {3, 34, 3},  {4, 91, 10}, {5, 69, 11},
-             {6, 39, 7},  {7, 14, 8},  {8, 74, 10}, {9, 51, 5},  {11, 28, 14},
-             {12, 28, 16}, {13, 5, 6},  {14, 5, 9},  {15, 20, 6}, {16, 40, 9},
-             {17, 40, 9}, {18, 41, 7}, {19, 42, 14}};
-    for (auto& t : T)
-        if (t.k == kind) {
-            *out_nw = t.nw;
-            *out_ns = t.ns;
-            return 0;
-        }
-    return RNG_ERR_BAD_ARG;
-}
-
-// fixed-seed witness/statement generator for any kind (test vectors for the
-// prover-service routes; same serialization rng_circ_from_scalars parses)
-int rng_witness_statement(int kind, uint64_t seed, uint64_t* out_w, uint64_t* out_s) {
-    try {
-        Wt w{(Fr*)out_w};
-        Wt s{(Fr*)out_s};
-        switch (kind) {
-            case 1: {
-                VdWitness vw;
-                VdStatement st;
-                vd_build_witness_statement(seed, vw, st);
-                w.sbal(vw.old_balance);
-                w.opening(vw.opening_elems, vw.opening_indices);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 2: {
-                VdWitness vw;
-                VwStatement st;
-                vw_build_witness_statement(seed, vw, st);
-                w.sbal(vw.old_balance);
-                w.opening(vw.opening_elems, vw.opening_indices);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 3: {
-                VocWitness vw;
-                VocStatement st;
-                voc_build_witness_statement(seed, vw, st);
-                w.sint(vw.old_intent);
-                w.opening(vw.opening_elems, vw.opening_idx);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 4: {
-                ValidityBundle b;
-                validity_bundle_build(seed, b);
-                const ValidityWitness& vw = b.vw[0];
-                w.sint(vw.old_intent);
-                w.opening(vw.intent_opening_elems, vw.intent_opening_idx);
-                w.in(vw.intent);
-                w.f(vw.new_amount_public_share);
-                w.sbal(vw.old_balance);
-                w.opening(vw.balance_opening_elems, vw.balance_opening_idx);
-                w.bal(vw.balance);
-                w.pms(vw.post_match_balance_shares);
-                s.st(b.vst[0].to_scalars());
-                break;
-            }
-            case 5: {
-                ValidityBundle b;
-                validity_bundle_build(seed, b);
-                FfWitness vw;
-                FfStatement st;
-                ff_build(b, 0, seed, vw, st);
-                w.in(vw.intent);
-                w.cs(vw.share_stream);
-                w.cs(vw.recovery_stream);
-                w.frs(vw.private_intent_shares, 5);
-                w.f(vw.new_amount_public_share);
-                w.sig(vw.sig);
-                w.sbal(vw.old_balance);
-                w.bal(vw.balance);
-                w.pms(vw.post_match_balance_shares);
-                w.opening(vw.opening_elems, vw.opening_idx);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 6: {
-                IoValidityWitness vw;
-                IoValidityStatement vs;
-                IoSettlementStatement ss;
-                io_bundle_build(seed, vw, vs, ss);
-                w.sint(vw.old_intent);
-                w.opening(vw.opening_elems, vw.opening_idx);
-                w.in(vw.intent);
-                s.st(vs.to_scalars());
-                break;
-            }
-            case 7: {
-                IoffWitness vw;
-                IoffStatement st;
-                ioff_build(seed, vw, st);
-                w.in(vw.intent);
-                w.cs(vw.share_stream);
-                w.cs(vw.recovery_stream);
-                w.frs(vw.private_shares, 5);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 8: {
-                NobWitness vw;
-                NobStatement st;
-                nob_build(seed, vw, st);
-                w.sbal(vw.new_balance);
-                w.bal(vw.balance);
-                w.pms(vw.post_match_balance_shares);
-                w.sbal(vw.existing_balance);
-                w.opening(vw.opening_elems, vw.opening_idx);
-                w.sig(vw.sig);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 9: {
-                ValidityBundle b;
-                validity_bundle_build(seed, b);
-                const ObValidityWitness& vw = b.ow[0];
-                w.sbal(vw.old_balance);
-                w.opening(vw.opening_elems, vw.opening_idx);
-                w.bal(vw.balance);
-                w.pms(vw.post_match_balance_shares);
-                s.st(b.ost[0].to_scalars());
-                break;
-            }
-            case 11: {
-                ValidityBundle b;
-                validity_bundle_build(seed, b);
-                const SettlementParty& p = b.sw.p[0];
-                w.in(p.intent);
-                w.f(p.pre_amount_share);
-                w.bal(p.input_balance);
-                w.pms(p.pre_in_shares);
-                w.bal(p.output_balance);
-                w.pms(p.pre_out_shares);
-                PubSettlementStatement st;
-                pub_settlement_statement_from_bundle(b, st);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 12: {
-                ValidityBundle b;
-                validity_bundle_build(seed, b);
-                const SettlementParty& p = b.sw.p[0];
-                w.in(p.intent);
-                w.f(p.pre_amount_share);
-                w.bal(p.input_balance);
-                w.pms(p.pre_in_shares);
-                w.bal(p.output_balance);
-                w.pms(p.pre_out_shares);
-                IbBoundedStatement st;
-                ib_bounded_statement_from_bundle(b, st);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 13: {
-                IoValidityWitness vw;
-                IoValidityStatement vs;
-                IoSettlementStatement ss;
-                io_bundle_build(seed, vw, vs, ss);
-                w.in(vw.intent);
-                s.st(ss.to_scalars());
-                break;
-            }
-            case 14: {
-                IoValidityWitness vw;
-                IoValidityStatement vs;
-                IoSettlementStatement ss;
-                io_bundle_build(seed, vw, vs, ss);
-                IoBoundedStatement st;
-                io_bounded_statement_build(seed, vw, ss, st);
-                w.in(vw.intent);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 15: {
-                NoteRedemptionWitness vw;
-                NoteRedemptionStatement st;
-                note_redemption_build(seed, vw, st);
-                w.opening(vw.opening_elems, vw.opening_idx);
-                s.st(st.to_scalars());
-                break;
-            }
-            case 16:
-            case 17:
-            case 18: {
-                VdWitness vw;
-                FeePaymentStatement st;
-                Note note;
-                int field = (kind == 17) ? 6 : 5;
-                fee_payment_build(seed, field, vw, st, note);
-                w.sbal(vw.old_balance);
-                w.opening(vw.opening_elems, vw.opening_indices);
-                std::vector<Fr> ss = {st.merkle_root, st.old_balance_nullifier,
-                                      st.new_balance_commitment, st.recovery_id,
-                                      st.new_fee_balance_share};
-                if (kind == 18) {
-                    w.f(note.blinder);
-                    ss.push_back(note.receiver);
-                    ss.push_back(native_note_commitment(note));
-                } else {
-                    auto nv = note.to_scalars();
-                    ss.insert(ss.end(), nv.begin(), nv.end());
-                }
-                s.st(ss);
-                break;
-            }
-            case 19: {
-                VdWitness vw;
-                FeePaymentStatement st;
-                Note note;
-                fee_payment_build(seed, 6, vw, st, note);
-                Lcg rng(seed ^ 0xE161A3A1E161A3A1ull);
-                u64 al[4] = {rng.next() | (rng.next() << 53),
-                             rng.next() | (rng.next() << 53), rng.next() & 0xFFFFFFFF, 0};
-                note.receiver = Fr::from_canonical(al);
-                JjScalar dk = jj_random_scalar(rng);
-                JjScalar k = jj_random_scalar(rng);
-                JjPoint pk = jj_pubkey(dk);
-                Fr plain[3] = {note.mint, note.amount, note.blinder};
-                JjCiphertext<3> ct = jj_elgamal_encrypt<3>(pk, k, plain);
-                w.sbal(vw.old_balance);
-                w.opening(vw.opening_elems, vw.opening_indices);
-                w.f(note.blinder);
-                w.f(Fr::from_canonical(k.v));
-                s.st({st.merkle_root, st.old_balance_nullifier, st.new_balance_commitment,
-                      st.recovery_id, st.new_fee_balance_share, note.receiver,
-                      native_note_commitment(note), ct.ephemeral_key.x,
-                      ct.ephemeral_key.y, ct.ciphertext[0], ct.ciphertext[1],
-                      ct.ciphertext[2], pk.x, pk.y});
-                break;
-            }
-            default:
-                return RNG_ERR_BAD_ARG;
-        }
-        return RNG_OK;
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_witness_statement: %s\n", e.what());
-        return RNG_ERR_BAD_ARG;
-    }
-}
-
-// Party-aware test vectors for the two per-party validity kinds (4 = intent-
-// and-balance validity, 9 = output-balance validity): the private-settlement
-// route takes FOUR external hints (party 0/1 of each), all from one seed's
-// consistent bundle (native_proof_manager.rs:554-590).
-int rng_witness_statement_party(int kind, uint64_t seed, uint64_t party,
-                                uint64_t* out_w, uint64_t* out_s) {
-    try {
-        Wt w{(Fr*)out_w};
-        Wt s{(Fr*)out_s};
-        int p = (int)(party & 1);
-        ValidityBundle b;
-        validity_bundle_build(seed, b);
-        if (kind == 4) {
-            const ValidityWitness& vw = b.vw[p];
-            w.sint(vw.old_intent);
-            w.opening(vw.intent_opening_elems, vw.intent_opening_idx);
-            w.in(vw.intent);
-            w.f(vw.new_amount_public_share);
-            w.sbal(vw.old_balance);
-            w.opening(vw.balance_opening_elems, vw.balance_opening_idx);
-            w.bal(vw.balance);
-            w.pms(vw.post_match_balance_shares);
-            s.st(b.vst[p].to_scalars());
-        } else if (kind == 9) {
-            const ObValidityWitness& vw = b.ow[p];
-            w.sbal(vw.old_balance);
-            w.opening(vw.opening_elems, vw.opening_idx);
-            w.bal(vw.balance);
-            w.pms(vw.post_match_balance_shares);
-            s.st(b.ost[p].to_scalars());
-        } else if (kind == 10) {
-            // the BUNDLE's settlement witness/statement (64/17 scalars, same
-            // order as rng_settlement_witness_statement).  Needed because
-            // validity_bundle_build mutates the settlement witness after
-            // building it (real Schnorr authorities on the input balances),
-            // so only the bundle's version links against the bundle's
-            // validity proofs.  `party` is ignored.
-            const SettlementWitness& sw = b.sw;
-            std::vector<Fr> ws;
-            for (int i = 0; i < 2; ++i) {
-                auto a = sw.p[i].obligation.to_scalars();
-                auto bi = sw.p[i].intent.to_scalars();
-                auto c = sw.p[i].input_balance.to_scalars();
-                auto d = sw.p[i].pre_in_shares.to_scalars();
-                auto e = sw.p[i].output_balance.to_scalars();
-                auto f = sw.p[i].pre_out_shares.to_scalars();
-                ws.insert(ws.end(), a.begin(), a.end());
-                ws.insert(ws.end(), bi.begin(), bi.end());
-                ws.push_back(sw.p[i].pre_amount_share);
-                ws.insert(ws.end(), c.begin(), c.end());
-                ws.insert(ws.end(), d.begin(), d.end());
-                ws.insert(ws.end(), e.begin(), e.end());
-                ws.insert(ws.end(), f.begin(), f.end());
-            }
-            auto ss = b.sst.to_scalars();
-            memcpy(out_w, ws.data(), ws.size() * sizeof(Fr));
-            memcpy(out_s, ss.data(), ss.size() * sizeof(Fr));
-        } else {
-            return RNG_ERR_BAD_ARG;
-        }
-        return RNG_OK;
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_witness_statement_party: %s\n", e.what());
-        return RNG_ERR_BAD_ARG;
-    }
-}
-
-// Build any circuit from caller-supplied witness/statement scalars (the
-// prover-service request shape).  `kind` table in include/rng_prover.h;
-// returns null if the witness does not satisfy the circuit.
-void* rng_circ_from_scalars(int kind, const uint64_t* witness64,
-                            const uint64_t* statement64) {
-    try {
-        Rd w{(const Fr*)witness64};
-        Rd s{(const Fr*)statement64};
-        const LinkLayouts& L = link_layouts();
-        PlonkCircuit cs;
-        switch (kind) {
-            case 1:
-            case 2: {  // valid deposit / withdrawal (witness 40)
-                VdWitness vw;
-                vw.old_balance = w.sbal();
-                w.opening(vw.opening_elems, vw.opening_indices);
-                if (kind == 1) {
-                    VdStatement st;
-                    st.deposit.from = s.f();
-                    st.deposit.token = s.f();
-                    st.deposit.amount = s.f();
-                    st.merkle_root = s.f();
-                    st.old_nullifier = s.f();
-                    st.new_commitment = s.f();
-                    st.recovery_id = s.f();
-                    st.new_amount_share = s.f();
-                    vd_apply_constraints(cs, vw, st);
-                } else {
-                    VwStatement st;
-                    st.to = s.f();
-                    st.token = s.f();
-                    st.amount = s.f();
-                    st.merkle_root = s.f();
-                    st.old_nullifier = s.f();
-                    st.new_commitment = s.f();
-                    st.recovery_id = s.f();
-                    st.new_amount_share = s.f();
-                    vw_apply_constraints(cs, vw, st);
-                }
-                break;
-            }
-            case 3: {  // valid order cancellation (witness 34)
-                VocWitness vw;
-                vw.old_intent = w.sint();
-                w.opening(vw.opening_elems, vw.opening_idx);
-                VocStatement st;
-                st.merkle_root = s.f();
-                st.old_intent_nullifier = s.f();
-                st.owner = s.f();
-                voc_apply_constraints(cs, vw, st);
-                break;
-            }
-            case 4: {  // intent-and-balance validity (witness 91)
-                ValidityWitness vw;
-                vw.old_intent = w.sint();
-                w.opening(vw.intent_opening_elems, vw.intent_opening_idx);
-                vw.intent = w.in();
-                vw.new_amount_public_share = w.f();
-                vw.old_balance = w.sbal();
-                w.opening(vw.balance_opening_elems, vw.balance_opening_idx);
-                vw.balance = w.bal();
-                vw.post_match_balance_shares = w.pms();
-                ValidityStatement st;
-                st.intent_merkle_root = s.f();
-                st.old_intent_nullifier = s.f();
-                st.intent_partial_private = s.f();
-                st.intent_partial_public = s.f();
-                st.intent_recovery_id = s.f();
-                st.balance_merkle_root = s.f();
-                st.old_balance_nullifier = s.f();
-                st.balance_partial_private = s.f();
-                st.balance_partial_public = s.f();
-                st.balance_recovery_id = s.f();
-                validity_apply_constraints(cs, vw, st, (int)L.ib_align, L.pg0, L.pg1);
-                break;
-            }
-            case 5: {  // first-fill validity (witness 69)
-                FfWitness vw;
-                vw.intent = w.in();
-                vw.share_stream = w.cs();
-                vw.recovery_stream = w.cs();
-                w.frs(vw.private_intent_shares, 5);
-                vw.new_amount_public_share = w.f();
-                vw.sig = w.sig();
-                vw.old_balance = w.sbal();
-                vw.balance = w.bal();
-                vw.post_match_balance_shares = w.pms();
-                w.opening(vw.opening_elems, vw.opening_idx);
-                FfStatement st;
-                st.merkle_root = s.f();
-                s.frs(st.intent_public_share, 4);
-                st.intent_private_share_commitment = s.f();
-                st.intent_recovery_id = s.f();
-                st.balance_partial_private = s.f();
-                st.balance_partial_public = s.f();
-                st.old_balance_nullifier = s.f();
-                st.balance_recovery_id = s.f();
-                ff_apply_constraints(cs, vw, st, (int)L.ib_align, L.pg0, L.pg1);
-                break;
-            }
-            case 6: {  // intent-only validity (witness 39)
-                IoValidityWitness vw;
-                vw.old_intent = w.sint();
-                w.opening(vw.opening_elems, vw.opening_idx);
-                vw.intent = w.in();
-                IoValidityStatement st;
-                st.owner = s.f();
-                st.merkle_root = s.f();
-                st.old_intent_nullifier = s.f();
-                st.new_amount_public_share = s.f();
-                st.partial_private = s.f();
-                st.partial_public = s.f();
-                st.recovery_id = s.f();
-                io_validity_apply_constraints(cs, vw, st, (int)L.io_align, L.io_off);
-                break;
-            }
-            case 7: {  // intent-only first fill (witness 14)
-                IoffWitness vw;
-                vw.intent = w.in();
-                vw.share_stream = w.cs();
-                vw.recovery_stream = w.cs();
-                w.frs(vw.private_shares, 5);
-                IoffStatement st;
-                st.owner = s.f();
-                st.intent_private_commitment = s.f();
-                st.recovery_id = s.f();
-                s.frs(st.intent_public_share, 5);
-                ioff_apply_constraints(cs, vw, st, (int)L.io_align, L.io_off);
-                break;
-            }
-            case 8: {  // new output balance (witness 74)
-                NobWitness vw;
-                vw.new_balance = w.sbal();
-                vw.balance = w.bal();
-                vw.post_match_balance_shares = w.pms();
-                vw.existing_balance = w.sbal();
-                w.opening(vw.opening_elems, vw.opening_idx);
-                vw.sig = w.sig();
-                NobStatement st;
-                st.existing_merkle_root = s.f();
-                st.existing_nullifier = s.f();
-                s.frs(st.pre_match_shares, 5);
-                st.partial_private = s.f();
-                st.partial_public = s.f();
-                st.recovery_id = s.f();
-                nob_apply_constraints(cs, vw, st, (int)L.ib_align, L.og0, L.og1);
-                break;
-            }
-            case 9: {  // output-balance validity (witness 51)
-                ObValidityWitness vw;
-                vw.old_balance = w.sbal();
-                w.opening(vw.opening_elems, vw.opening_idx);
-                vw.balance = w.bal();
-                vw.post_match_balance_shares = w.pms();
-                ObValidityStatement st;
-                st.merkle_root = s.f();
-                st.old_balance_nullifier = s.f();
-                st.partial_private = s.f();
-                st.partial_public = s.f();
-                st.recovery_id = s.f();
-                ob_validity_apply_constraints(cs, vw, st, (int)L.ib_align, L.og0, L.og1);
-                break;
-            }
-            case 11: {  // ib public settlement (witness 28)
-                SettlementParty p = w.party_no_ob();
-                PubSettlementStatement st;
-                st.obligation = s.ob();
-                st.amount_public_share = s.f();
-                st.in_shares = s.pms();
-                st.out_shares = s.pms();
-                st.relayer_fee_repr = s.f();
-                st.protocol_fee_repr = s.f();
-                st.relayer_fee_recipient = s.f();
-                pub_settlement_apply_constraints(cs, p, st, (int)L.ib_align, L.pg0,
-                                                 L.og0);
-                break;
-            }
-            case 12: {  // ib bounded settlement (witness 28)
-                SettlementParty p = w.party_no_ob();
-                IbBoundedStatement st;
-                st.bmr.internal_party_input_token = s.f();
-                st.bmr.internal_party_output_token = s.f();
-                st.bmr.min_internal_party_amount_in = s.f();
-                st.bmr.max_internal_party_amount_in = s.f();
-                st.bmr.price_repr = s.f();
-                st.bmr.block_deadline = s.f();
-                st.amount_public_share = s.f();
-                st.in_shares = s.pms();
-                st.out_shares = s.pms();
-                st.internal_relayer_fee_repr = s.f();
-                st.external_relayer_fee_repr = s.f();
-                st.relayer_fee_recipient = s.f();
-                ib_bounded_apply_constraints(cs, p, st, (int)L.ib_align, L.pg0, L.og0);
-                break;
-            }
-            case 13: {  // io public settlement (witness 5)
-                Intent in = w.in();
-                IoSettlementStatement st;
-                st.obligation = s.ob();
-                st.relayer_fee_repr = s.f();
-                st.relayer_fee_recipient = s.f();
-                io_settlement_apply_constraints(cs, in, st);
-                break;
-            }
-            case 14: {  // io bounded settlement (witness 5)
-                Intent in = w.in();
-                IoBoundedStatement st;
-                st.bmr.internal_party_input_token = s.f();
-                st.bmr.internal_party_output_token = s.f();
-                st.bmr.min_internal_party_amount_in = s.f();
-                st.bmr.max_internal_party_amount_in = s.f();
-                st.bmr.price_repr = s.f();
-                st.bmr.block_deadline = s.f();
-                st.internal_relayer_fee_repr = s.f();
-                st.external_relayer_fee_repr = s.f();
-                st.relayer_fee_recipient = s.f();
-                io_bounded_apply_constraints(cs, in, st, (int)L.io_align, L.io_off);
-                break;
-            }
-            case 15: {  // note redemption (witness 20)
-                NoteRedemptionWitness vw;
-                w.opening(vw.opening_elems, vw.opening_idx);
-                NoteRedemptionStatement st;
-                st.note = s.note();
-                st.note_root = s.f();
-                st.note_nullifier = s.f();
-                note_redemption_apply_constraints(cs, vw, st);
-                break;
-            }
-            case 16:
-            case 17:
-            case 18: {  // fee payments (witness 40 [+1 blinder for 18])
-                VdWitness vw;
-                vw.old_balance = w.sbal();
-                w.opening(vw.opening_elems, vw.opening_indices);
-                Fr blinder = (kind == 18) ? w.f() : Fr::zero();
-                int field = (kind == 17) ? 6 : 5;
-                int note_mode = (kind == 18) ? 1 : 0;
-                std::vector<Fr> ss;
-                int nst = (note_mode == 0) ? 9 : 7;
-                for (int i = 0; i < nst; ++i) ss.push_back(s.f());
-                fee_payment_apply_constraints(cs, vw, blinder, field, note_mode,
-                                              kind != 17, ss);
-                break;
-            }
-            case 19: {  // private protocol fee (witness 42)
-                VdWitness vw;
-                vw.old_balance = w.sbal();
-                w.opening(vw.opening_elems, vw.opening_indices);
-                Fr blinder = w.f();
-                Fr enc_k = w.f();
-                std::vector<Fr> ss;
-                for (int i = 0; i < 14; ++i) ss.push_back(s.f());
-                fee_private_protocol_apply_constraints(cs, vw, blinder, enc_k, ss);
-                break;
-            }
-            default:
-                fprintf(stderr, "rng_circ_from_scalars: unknown kind %d\n", kind);
-                return nullptr;
-        }
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_from_scalars(kind=%d): %s\n", kind, why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_from_scalars: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// VALID ORDER CANCELLATION circuit (valid_order_cancellation.rs)
-void* rng_circ_build_valid_order_cancellation(uint64_t seed) {
-    try {
-        VocWitness w;
-        VocStatement st;
-        voc_build_witness_statement(seed, w, st);
-        PlonkCircuit cs;
-        voc_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_valid_order_cancellation: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_valid_order_cancellation: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// circuit builders from caller-supplied witness/statement scalars (the shape
-// the external prover service receives — api_types.rs requests; Montgomery
-// limbs, field order per the reference structs)
-void* rng_circ_vbc_from_scalars(const uint64_t* witness12, const uint64_t* statement13) {
-    try {
-        VbcWitness w;
-        VbcStatement st;
-        vbc_witness_from_scalars((const Fr*)witness12, w);
-        vbc_statement_from_scalars((const Fr*)statement13, st);
-        PlonkCircuit cs;
-        vbc_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_vbc_from_scalars: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_vbc_from_scalars: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-void* rng_circ_settlement_from_scalars(const uint64_t* witness64,
-                                       const uint64_t* statement17) {
-    try {
-        SettlementWitness w;
-        SettlementStatement st;
-        settlement_witness_from_scalars((const Fr*)witness64, w);
-        settlement_statement_from_scalars((const Fr*)statement17, st);
-        PlonkCircuit cs;
-        settlement_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_settlement_from_scalars: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_settlement_from_scalars: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// expose the fixed-seed witness/statement generators (bench/test data)
-void rng_vbc_witness_statement(uint64_t seed, uint64_t* witness12, uint64_t* statement13) {
-    VbcWitness w;
-    VbcStatement st;
-    vbc_build_witness_statement(seed, w, st);
-    auto ws = w.to_scalars();
-    auto ss = st.to_scalars();
-    memcpy(witness12, ws.data(), ws.size() * sizeof(Fr));
-    memcpy(statement13, ss.data(), ss.size() * sizeof(Fr));
-}
-void rng_settlement_witness_statement(uint64_t seed, uint64_t* witness64,
-                                      uint64_t* statement17) {
-    SettlementWitness w;
-    SettlementStatement st;
-    settlement_build_witness_statement(seed, w, st);
-    std::vector<Fr> ws;
-    for (int i = 0; i < 2; ++i) {
-        auto a = w.p[i].obligation.to_scalars();
-        auto b = w.p[i].intent.to_scalars();
-        auto c = w.p[i].input_balance.to_scalars();
-        auto d = w.p[i].pre_in_shares.to_scalars();
-        auto e = w.p[i].output_balance.to_scalars();
-        auto f = w.p[i].pre_out_shares.to_scalars();
-        ws.insert(ws.end(), a.begin(), a.end());
-        ws.insert(ws.end(), b.begin(), b.end());
-        ws.push_back(w.p[i].pre_amount_share);
-        ws.insert(ws.end(), c.begin(), c.end());
-        ws.insert(ws.end(), d.begin(), d.end());
-        ws.insert(ws.end(), e.begin(), e.end());
-        ws.insert(ws.end(), f.begin(), f.end());
-    }
-    auto ss = st.to_scalars();
-    memcpy(witness64, ws.data(), ws.size() * sizeof(Fr));
-    memcpy(statement17, ss.data(), ss.size() * sizeof(Fr));
-}
-
-// linked test circuit: `count` link-group values derived from value_seed,
-// placed at (alignment, offset), plus filler gates scaled by `scale` —
-// two different scales give two circuits of different domain size whose
-// group values coincide (the cross-circuit linking shape: a validity proof
-// linking into the settlement proof across domains).
-void* rng_testcirc_build_linked(uint64_t value_seed, uint64_t scale, uint64_t alignment,
-                                uint64_t offset, uint64_t count) {
-    try {
-        PlonkCircuit cs;
-        cs.create_link_group("xlink", (int)alignment, (int64_t)offset);
-        Lcg vr(value_seed);
-        for (uint64_t k = 0; k < count; ++k) {
-            Var v = cs.create_variable(vr.fr());
-            cs.add_to_link_group(v, "xlink");
-        }
-        build_mixed_circuit(cs, value_seed + 1000 * scale, scale);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_testcirc_build_linked: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_testcirc_build_linked: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// `Valid Deposit` circuit builder (zk_circuits/valid_deposit.rs)
-void* rng_circ_build_valid_deposit(uint64_t seed) {
-    try {
-        VdWitness w;
-        VdStatement st;
-        vd_build_witness_statement(seed, w, st);
-        PlonkCircuit cs;
-        vd_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_valid_deposit: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_valid_deposit: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-// `Valid Withdrawal` circuit builder (zk_circuits/valid_withdrawal.rs)
-void* rng_circ_build_valid_withdrawal(uint64_t seed) {
-    try {
-        VdWitness w;
-        VwStatement st;
-        vw_build_witness_statement(seed, w, st);
-        PlonkCircuit cs;
-        vw_apply_constraints(cs, w, st);
-        std::string why;
-        if (!cs.check_satisfied(&why)) {
-            fprintf(stderr, "rng_circ_build_valid_withdrawal: %s\n", why.c_str());
-            return nullptr;
-        }
-        return new CircuitTables(cs.finalize());
-    } catch (const std::exception& e) {
-        fprintf(stderr, "rng_circ_build_valid_withdrawal: %s\n", e.what());
-        return nullptr;
-    }
-}
-
-uint64_t rng_circ_num_link_groups(void* t) {
-    return static_cast<CircuitTables*>(t)->link_groups.size();
-}
-// out: per group 3 u64 (alignment, grid offset, count), in creation order
-void rng_circ_link_groups(void* t_, uint64_t* out) {
-    auto* t = static_cast<CircuitTables*>(t_);
-    for (size_t i = 0; i < t->link_groups.size(); ++i) {
-        out[3 * i] = t->link_groups[i].alignment;
-        out[3 * i + 1] = t->link_groups[i].offset;
-        out[3 * i + 2] = t->link_groups[i].count;
-    }
-}
-
-// native Poseidon2 hash (for cross-checks vs the oracle's restatement)
-void rng_poseidon_hash(const uint64_t* inputs_mont, uint64_t n, uint64_t* out_mont) {
-    std::vector<Fr> in(n);
-    memcpy(in.data(), inputs_mont, n * sizeof(Fr));
-    Fr r = poseidon_hash(in.data(), n);
-    memcpy(out_mont, r.l, 32);
-}
-
-uint64_t rng_circ_n(void* t) { return static_cast<CircuitTables*>(t)->n; }
-uint64_t rng_circ_npub(void* t) { return static_cast<CircuitTables*>(t)->num_public; }
-
-// selectors: 13*n*4 u64; sigma: 5*n u64; wires: 5*n*4 u64; pubs: npub*4 u64
-void rng_circ_get(void* t_, uint64_t* selectors, uint64_t* sigma, uint64_t* wires,
-                  uint64_t* pubs) {
-    auto* t = static_cast<CircuitTables*>(t_);
-    memcpy(selectors, t->selectors.data(), t->selectors.size() * sizeof(Fr));
-    memcpy(sigma, t->sigma.data(), t->sigma.size() * 8);
-    memcpy(wires, t->wires.data(), t->wires.size() * sizeof(Fr));
-    if (!t->public_inputs.empty())
-        memcpy(pubs, t->public_inputs.data(), t->public_inputs.size() * sizeof(Fr));
-}
-
-void rng_circ_free(void* t) { delete static_cast<CircuitTables*>(t); }
+#include "circuit_abi.hpp"
 
 // field-mul microbenchmark: returns ms per launch; variant 0 = 64-bit CIOS,
 // 1 = 32-bit CIOS; dep = dependent chain
@@ -4516,15 +2605,7 @@ int rng_pairing_check(const uint64_t* p1, const uint64_t* q1, const uint64_t* p2
 // host G1 addition on 9-u64 affine records (for combining per-rank MSM shard
 // results after the RCCL/gloo exchange — SURVEY.md §8e; host-side, tiny)
 void rng_g1_add_affine(const uint64_t* a9, const uint64_t* b9, uint64_t* out9) {
-    auto load = [](const uint64_t* r) {
-        G1Jac j;
-        if (r[8]) return G1Jac::identity();
-        G1Aff a;
-        memcpy(a.x.l, r, 32);
-        memcpy(a.y.l, r + 4, 32);
-        return G1Jac::from_affine(a);
-    };
-    G1Jac s = load(a9).add(load(b9));
+    G1Jac s = g1_record_load_jac(a9).add(g1_record_load_jac(b9));
     jac_to_affine_record(s, out9);
 }
 
@@ -4650,7 +2731,9 @@ int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wi
     const uint64_t n = impl.n;
     bool dev = mode == 1;
     if (mode == 0)  // rng_prove_cohort sends k = 1 down the single-proof path
-        dev = (batch == 1 ? z_device_single() : z_device_cohort()) && n <= PERM_MAX_N;
+        dev = ProverEnv::on(prover_env().z_device, batch == 1 ? Z_DEVICE_DEFAULT_SINGLE
+                                                              : Z_DEVICE_DEFAULT_COHORT) &&
+              n <= PERM_MAX_N;
     if (dev)
         return perm_product_hosted(wires, impl.sig_evals_dev, impl.wpow_dev, impl.k, beta_gamma, n,
                                    batch, out_z);
@@ -4667,20 +2750,10 @@ int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wi
 uint64_t rng_pk_n(RngProvingKey* pk) { return pk->impl.n; }
 // out: 18 affine records (13 selector comms, 5 sigma comms)
 void rng_pk_comms(RngProvingKey* pk, uint64_t* out) {
-    auto store = [&](const G1Aff& a, bool inf, uint64_t* rec) {
-        if (inf) {  // canonical infinity record: zeroed coords + flag
-            memset(rec, 0, 8 * 8);
-            rec[8] = 1;
-            return;
-        }
-        memcpy(rec, a.x.l, 32);
-        memcpy(rec + 4, a.y.l, 32);
-        rec[8] = 0;
-    };
     for (int s = 0; s < 13; ++s)
-        store(pk->impl.sel_comms[s], pk->impl.sel_inf[s], out + 9 * s);
+        g1_record_store(pk->impl.sel_comms[s], pk->impl.sel_inf[s], out + 9 * s);
     for (int j = 0; j < 5; ++j)
-        store(pk->impl.sig_comms[j], pk->impl.sig_inf[j], out + 9 * (13 + j));
+        g1_record_store(pk->impl.sig_comms[j], pk->impl.sig_inf[j], out + 9 * (13 + j));
 }
 
 // Full PlonK verifier with the real BN254 pairing (replaces
@@ -4706,18 +2779,12 @@ int rng_verify(RngCtx* ctx, const RngProvingKey* pkw, const uint64_t* public_inp
     if (pk.npub > 0 && !public_inputs) return RNG_ERR_BAD_ARG;
     const Fr* pubs = (const Fr*)public_inputs;
     // --- deserialize proof (layout: include/rng_prover.h) ---
+    G1Aff affs[13];
     G1Jac comms[13];
     bool infs[13];
     for (int i = 0; i < 13; ++i) {
-        infs[i] = proof[9 * i + 8] != 0;
-        if (infs[i]) {
-            comms[i] = G1Jac::identity();
-        } else {
-            G1Aff a;
-            memcpy(a.x.l, proof + 9 * i, 32);
-            memcpy(a.y.l, proof + 9 * i + 4, 32);
-            comms[i] = G1Jac::from_affine(a);
-        }
+        infs[i] = g1_record_load(proof + 9 * i, &affs[i]);
+        comms[i] = infs[i] ? G1Jac::identity() : G1Jac::from_affine(affs[i]);
     }
     // Reject malformed proofs BEFORE transcript replay / pairing: the
     // reference's arkworks deserialization enforces curve membership and
@@ -4730,9 +2797,7 @@ int rng_verify(RngCtx* ctx, const RngProvingKey* pkw, const uint64_t* public_inp
             if (infs[i]) continue;
             const uint64_t* rec = proof + 9 * i;
             if (Fq::geq_mod(rec) || Fq::geq_mod(rec + 4)) return RNG_ERR_VERIFY;
-            Fq x, y;
-            memcpy(x.l, rec, 32);
-            memcpy(y.l, rec + 4, 32);
+            const Fq &x = affs[i].x, &y = affs[i].y;
             if (!y.sqr().eq(x.sqr().mul(x).add(b3))) return RNG_ERR_VERIFY;
         }
         for (int i = 0; i < 10; ++i)
@@ -4748,12 +2813,7 @@ int rng_verify(RngCtx* ctx, const RngProvingKey* pkw, const uint64_t* public_inp
     // --- transcript replay ---
     HostTranscript tr;
     h_transcript_init(tr, pk, pubs);
-    auto append_comm = [&](int i) {
-        G1Aff a;
-        memcpy(a.x.l, proof + 9 * i, 32);
-        memcpy(a.y.l, proof + 9 * i + 4, 32);
-        tr.append_g1(a, infs[i]);
-    };
+    auto append_comm = [&](int i) { tr.append_g1(affs[i], infs[i]); };
     for (int j = 0; j < 5; ++j) append_comm(j);
     Fr beta = tr.challenge(), gamma = tr.challenge();
     append_comm(5);
@@ -4769,9 +2829,10 @@ int rng_verify(RngCtx* ctx, const RngProvingKey* pkw, const uint64_t* public_inp
     Fr u = tr.challenge();
 
     Fr w = h_fr_root_of_unity((uint32_t)n);
-    Fr zeta_n = zeta.pow_u64(n);
-    Fr zh_zeta = zeta_n.sub(Fr::one());
-    Fr l1_zeta = zh_zeta.mul(Fr::from_u64(n).mul(zeta.sub(Fr::one())).inverse());
+    // the provers' own linearization scalars (plonk_rounds.hpp), applied to
+    // commitments here
+    const LinScalars ls = lin_scalars(pk.k, n, wire_evals, sigma_evals, z_shift_eval, beta,
+                                      gamma, alpha, zeta);
     Fr pi_zeta = Fr::zero();
     {
         std::vector<Fr> dens(pk.npub);
@@ -4785,48 +2846,23 @@ int rng_verify(RngCtx* ctx, const RngProvingKey* pkw, const uint64_t* public_inp
         if (pk.npub) {
             dens = hbatch_inverse(dens);
             for (uint64_t i = 0; i < pk.npub; ++i)
-                pi_zeta = pi_zeta.add(pubs[i].mul(wis[i]).mul(zh_zeta).mul(dens[i]));
+                pi_zeta = pi_zeta.add(pubs[i].mul(wis[i]).mul(ls.zh_zeta).mul(dens[i]));
         }
     }
-    auto p5 = [](const Fr& x) {
-        Fr x2 = x.sqr();
-        return x2.sqr().mul(x);
-    };
-    const Fr* wb = wire_evals;
-    Fr fbar = Fr::one(), Bbar = Fr::one();
-    for (int j = 0; j < 5; ++j)
-        fbar = fbar.mul(wb[j].add(beta.mul(pk.k[j]).mul(zeta)).add(gamma));
-    for (int j = 0; j < 4; ++j)
-        Bbar = Bbar.mul(wb[j].add(beta.mul(sigma_evals[j])).add(gamma));
     Fr ED = pi_zeta.neg()
-                .add(alpha.mul(z_shift_eval).mul(Bbar).mul(wb[4].add(gamma)))
-                .add(alpha.sqr().mul(l1_zeta));
+                .add(alpha.mul(z_shift_eval).mul(ls.Bbar).mul(wire_evals[4].add(gamma)))
+                .add(alpha.sqr().mul(ls.l1_zeta));
 
-    // [D]
+    // [D]; commitments at infinity are skipped
     G1Jac D = G1Jac::identity();
-    auto addsel = [&](int i, const Fr& s) {
-        if (pk.sel_inf[i]) return;
-        D = D.add(jac_mul_canon(G1Jac::from_affine(pk.sel_comms[i]), s));
-    };
-    addsel(11, Fr::one());
-    for (int j = 0; j < 4; ++j) addsel(j, wb[j]);
-    addsel(4, wb[0].mul(wb[1]));
-    addsel(5, wb[2].mul(wb[3]));
-    for (int j = 0; j < 4; ++j) addsel(6 + j, p5(wb[j]));
-    addsel(12, wb[0].mul(wb[1]).mul(wb[2]).mul(wb[3]).mul(wb[4]));
-    addsel(10, wb[4].neg());
-    D = D.add(jac_mul_canon(comms[5], alpha.mul(fbar).add(alpha.sqr().mul(l1_zeta))));
+    for (int i = 0; i < 13; ++i)
+        if (!pk.sel_inf[i])
+            D = D.add(jac_mul_canon(G1Jac::from_affine(pk.sel_comms[i]), ls.sel[i]));
+    D = D.add(jac_mul_canon(comms[COMM_Z], ls.z));
     if (!pk.sig_inf[4])
-        D = D.add(jac_mul_canon(G1Jac::from_affine(pk.sig_comms[4]),
-                                alpha.mul(beta).mul(z_shift_eval).mul(Bbar).neg()));
-    {
-        Fr zpow = zh_zeta.neg();
-        Fr step = zeta.pow_u64(n + 2);
-        for (int i = 0; i < 5; ++i) {
-            D = D.add(jac_mul_canon(comms[6 + i], zpow));
-            zpow = zpow.mul(step);
-        }
-    }
+        D = D.add(jac_mul_canon(G1Jac::from_affine(pk.sig_comms[4]), ls.sigma4));
+    for (int i = 0; i < 5; ++i)
+        D = D.add(jac_mul_canon(comms[COMM_CHUNKS + i], ls.chunk[i]));
     // F, E
     G1Jac F = D;
     Fr E = ED;
@@ -4939,9 +2975,8 @@ int rng_link_proofs(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* hint_a
     tr.append_u64(group_size);
     auto append_rec = [&](const uint64_t* rec) {
         G1Aff a;
-        memcpy(a.x.l, rec, 32);
-        memcpy(a.y.l, rec + 4, 32);
-        tr.append_g1(a, rec[8] != 0);
+        bool inf = g1_record_load(rec, &a);
+        tr.append_g1(a, inf);
     };
     append_rec(hint_a + 4 * hn);
     append_rec(hint_b + 4 * hn);
@@ -4954,12 +2989,8 @@ int rng_link_proofs(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* hint_a
     G1Aff wc;
     bool winf;
     if (commit_dev(&ctx->impl, W, &wc, &winf) != RNG_OK) return RNG_ERR_HIP;
-    memcpy(out_link_proof, qc.x.l, 32);
-    memcpy(out_link_proof + 4, qc.y.l, 32);
-    out_link_proof[8] = qinf ? 1 : 0;
-    memcpy(out_link_proof + 9, wc.x.l, 32);
-    memcpy(out_link_proof + 13, wc.y.l, 32);
-    out_link_proof[17] = winf ? 1 : 0;
+    g1_record_store(qc, qinf, out_link_proof);
+    g1_record_store(wc, winf, out_link_proof + 9);
     return RNG_OK;
 }
 

@@ -333,3 +333,118 @@ def test_cohort_large_domain_bit_exact(orc):
         assert np.array_equal(single, proofs[157 * p:157 * (p + 1)]), \
             f"large-domain cohort proof {p} differs"
     ctx.close()
+
+
+def test_cohort_distinct_witnesses(orc):
+    """k = 3 DIFFERENT witnesses and public inputs under one proving key: every
+    cohort proof and hint equals rng_prove on that witness and seed, proof 1
+    equals the oracle's, and rng_verify binds proof 2 to its own public
+    inputs.  (The other cohort tests tile one witness k times and cannot see
+    a slip in per-proof indexing of wires, public inputs or hints.)"""
+    from renegade_amd import load_prover
+    plib = load_prover()
+    if not plib.gpu_available:
+        pytest.skip("no GPU")
+    lib = plib.lib
+    lib.rng_circ_build_settlement.restype = ctypes.c_void_p
+    lib.rng_circ_build_settlement.argtypes = [ctypes.c_uint64]
+    lib.rng_circ_n.restype = ctypes.c_uint64
+    lib.rng_circ_n.argtypes = [ctypes.c_void_p]
+    lib.rng_circ_npub.restype = ctypes.c_uint64
+    lib.rng_circ_npub.argtypes = [ctypes.c_void_p]
+    lib.rng_circ_get.argtypes = [ctypes.c_void_p, U64P, U64P, U64P, U64P]
+    lib.rng_circ_free.argtypes = [ctypes.c_void_p]
+    lib.rng_preprocess.restype = ctypes.c_void_p
+    lib.rng_preprocess.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.rng_pk_free.argtypes = [ctypes.c_void_p]
+    lib.rng_prove.argtypes = [ctypes.c_void_p, ctypes.c_void_p, U64P, U64P,
+                              ctypes.c_uint64, U64P, U64P]
+    lib.rng_prove_cohort.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_uint64, U64P, U64P, U64P, U64P, U64P]
+    lib.rng_verify.argtypes = [ctypes.c_void_p, ctypes.c_void_p, U64P, U64P]
+    lib.rng_verify.restype = ctypes.c_int
+
+    tables = []
+    for cseed in (42, 43, 44):
+        h = lib.rng_circ_build_settlement(cseed)
+        assert h
+        n, npub = int(lib.rng_circ_n(h)), int(lib.rng_circ_npub(h))
+        sel = np.zeros(13 * n * 4, dtype=np.uint64)
+        sigma = np.zeros(5 * n, dtype=np.uint64)
+        wires = np.zeros(5 * n * 4, dtype=np.uint64)
+        pubs = np.zeros(npub * 4, dtype=np.uint64)
+        lib.rng_circ_get(h, ptr(sel), ptr(sigma), ptr(wires), ptr(pubs))
+        lib.rng_circ_free(h)
+        tables.append(dict(n=n, npub=npub, sel=sel, sigma=sigma, wires=wires, pubs=pubs))
+    t0 = tables[0]
+    n, npub = t0["n"], t0["npub"]
+    assert (n, npub) == (4096, 17)
+    for a in range(3):
+        t = tables[a]
+        # one circuit, three witnesses: same tables, different wires and inputs
+        assert (t["n"], t["npub"]) == (n, npub)
+        assert np.array_equal(t["sel"], t0["sel"])
+        assert np.array_equal(t["sigma"], t0["sigma"])
+        for b in range(a):
+            assert not np.array_equal(t["wires"], tables[b]["wires"])
+            assert not np.array_equal(t["pubs"], tables[b]["pubs"])
+
+    power = max(4, n.bit_length())
+    ptau = orc.srs_generate_ptau(power, seed=42)
+    max_degree = (1 << power) + 2
+    ctx = plib.init(ptau, max_degree)
+
+    class Desc(ctypes.Structure):
+        _fields_ = [("n", ctypes.c_uint64), ("num_public", ctypes.c_uint64),
+                    ("selectors", U64P), ("sigma", U64P),
+                    ("num_link_groups", ctypes.c_uint64), ("link_offsets", U64P)]
+
+    pk = lib.rng_preprocess(ctx.h, ctypes.byref(Desc(n, npub, ptr(t0["sel"]),
+                                                     ptr(t0["sigma"]), 0, None)))
+    assert pk
+    k = 3
+    seeds = np.array([31, 32, 31], dtype=np.uint64)
+    wires_all = np.concatenate([t["wires"] for t in tables])
+    pubs_all = np.concatenate([t["pubs"] for t in tables])
+    hint_len = 4 * (n + 2) + 9
+    proofs = np.zeros(157 * k, dtype=np.uint64)
+    hints = np.zeros(hint_len * k, dtype=np.uint64)
+    rc = lib.rng_prove_cohort(ctx.h, ctypes.c_void_p(pk), k, ptr(wires_all),
+                              ptr(pubs_all), ptr(seeds), ptr(proofs), ptr(hints))
+    assert rc == 0, f"rng_prove_cohort rc={rc}"
+    for p, t in enumerate(tables):
+        single = np.zeros(157, dtype=np.uint64)
+        shint = np.zeros(hint_len, dtype=np.uint64)
+        assert lib.rng_prove(ctx.h, ctypes.c_void_p(pk), ptr(t["wires"]), ptr(t["pubs"]),
+                             ctypes.c_uint64(int(seeds[p])), ptr(single),
+                             ptr(shint)) == 0
+        assert np.array_equal(proofs[157 * p:157 * (p + 1)], single), \
+            f"cohort proof {p} differs from rng_prove on its own witness"
+        assert np.array_equal(hints[hint_len * p:hint_len * (p + 1)], shint), \
+            f"cohort hint {p} differs"
+
+    # proof 1 against the oracle prover
+    o = orc.lib
+    o.orc_plonk_preprocess.restype = ctypes.c_void_p
+    o.orc_plonk_preprocess.argtypes = [ctypes.c_uint64, ctypes.c_uint64, U64P, U64P,
+                                       U64P, ctypes.c_uint64]
+    o.orc_plonk_prove.argtypes = [ctypes.c_void_p, U64P, U64P, ctypes.c_uint64, U64P]
+    g1, _, _ = orc.srs_parse(ptau, max_degree)
+    srs_records = np.ascontiguousarray(g1).reshape(-1)
+    opk = o.orc_plonk_preprocess(n, npub, ptr(t0["sel"]), ptr(t0["sigma"]),
+                                 ptr(srs_records), max_degree + 1)
+    assert opk
+    orc_proof = np.zeros(157, dtype=np.uint64)
+    assert o.orc_plonk_prove(ctypes.c_void_p(opk), ptr(tables[1]["wires"]),
+                             ptr(tables[1]["pubs"]), ctypes.c_uint64(32),
+                             ptr(orc_proof)) == 0
+    assert np.array_equal(proofs[157:314], orc_proof), "cohort proof 1 != oracle proof"
+
+    # proof 2 verifies under its own public inputs only
+    proof2 = np.ascontiguousarray(proofs[314:471])
+    assert lib.rng_verify(ctx.h, ctypes.c_void_p(pk), ptr(tables[2]["pubs"]),
+                          ptr(proof2)) == 0
+    assert lib.rng_verify(ctx.h, ctypes.c_void_p(pk), ptr(tables[0]["pubs"]),
+                          ptr(proof2)) != 0
+    lib.rng_pk_free(ctypes.c_void_p(pk))
+    ctx.close()
