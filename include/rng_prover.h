@@ -99,7 +99,9 @@ int rng_ntt_last_times(double out_ms[2]);
 
 /* In-place radix-2 NTT over BN254 Fr, natural order in/out,
  * data = batch * n elements of 4 u64 Montgomery limbs (host buffer).
- * n power of two, 2 <= n <= 2^26. */
+ * n power of two, 2 <= n <= 2^24 (a row of the two-pass split must fit one
+ * workgroup's LDS), batch >= 1; anything else is RNG_ERR_BAD_ARG.  The same
+ * bounds hold for the device-resident variants below. */
 int rng_ntt_fr(RngCtx* ctx, uint64_t* data, uint64_t n, uint64_t batch, int inverse);
 
 /* MSM over BN254 G1: bases = n * 8 u64 (affine x,y Montgomery; no points at
@@ -111,8 +113,10 @@ int rng_msm_g1(RngCtx* ctx, const uint64_t* bases, const uint64_t* scalars,
 /* Device-resident variants for benchmarking/pipelining (inputs already in
  * HBM; see rng_dbuf_*). */
 int rng_ntt_fr_dev(RngCtx* ctx, void* dev_data, uint64_t n, uint64_t batch, int inverse);
-/* out-of-place: result lands in dev_out (dev_in preserved for n > 1024;
- * for n <= 1024 the single-workgroup path runs in dev_in then copies). */
+/* out-of-place: result lands in dev_out; dev_in is scratch on return, for
+ * every n (n <= 1024 transforms in dev_in and copies, n > 1024 writes its
+ * first pass back into dev_in).  dev_in == dev_out is allowed for n <= 1024
+ * and gives the in-place result; for n > 1024 it is RNG_ERR_BAD_ARG. */
 int rng_ntt_fr_dev_oop(RngCtx* ctx, void* dev_in, void* dev_out, uint64_t n,
                        uint64_t batch, int inverse);
 int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,

@@ -86,6 +86,20 @@ void orc_ntt(u64* data, u64 n, int inverse) {
     else ntt_forward(a, n);
 }
 
+// Horner evaluation of n Montgomery coefficients at npts Montgomery points.
+void orc_fr_poly_eval(const u64* coeffs, u64 n, const u64* points, u64 npts, u64* out) {
+    fr_poly_eval(reinterpret_cast<const Fr*>(coeffs), n,
+                 reinterpret_cast<const Fr*>(points), npts, reinterpret_cast<Fr*>(out));
+}
+
+// out[k] = first * base^k for k < count (Montgomery in/out).
+void orc_fr_geom_table(const u64* first, const u64* base, u64 count, u64* out) {
+    Fr f, b;
+    memcpy(f.l, first, 32);
+    memcpy(b.l, base, 32);
+    fr_geom_table(f, b, count, reinterpret_cast<Fr*>(out));
+}
+
 void orc_coset_ntt(u64* data, u64 n, const u64* g_mont, int inverse) {
     Fr* a = reinterpret_cast<Fr*>(data);
     Fr g;

@@ -8,6 +8,7 @@
 #pragma once
 #include <vector>
 #include <cassert>
+#include <omp.h>
 #include "field.hpp"
 
 namespace oracle {
@@ -59,6 +60,38 @@ inline void ntt_inverse(Fr* a, size_t n) {
     ntt_core(a, n, w.inverse());
     Fr ninv = Fr::from_u64((u64)n).inverse();
     for (size_t i = 0; i < n; ++i) a[i] = a[i] * ninv;
+}
+
+// ---- definition-level references for sizes where ntt_core is too slow ----
+// Both are plain loops over Fr and share no code with ntt_core.
+
+// out[i] = sum_j coeffs[j] * points[i]^j (Horner), one thread per point.
+inline void fr_poly_eval(const Fr* coeffs, size_t n, const Fr* points, size_t npts,
+                         Fr* out) {
+#pragma omp parallel for schedule(dynamic, 1)
+    for (size_t i = 0; i < npts; ++i) {
+        Fr acc = Fr::zero();
+        for (size_t j = n; j-- > 0;) acc = acc * points[i] + coeffs[j];
+        out[i] = acc;
+    }
+}
+
+// out[k] = first * base^k for k < count.  Each thread fills one contiguous
+// chunk, started with a single pow and continued by repeated multiplication.
+inline void fr_geom_table(const Fr& first, const Fr& base, size_t count, Fr* out) {
+    size_t threads = (size_t)omp_get_max_threads();
+    size_t chunk = (count + threads - 1) / threads;
+#pragma omp parallel for schedule(static, 1)
+    for (size_t t = 0; t < threads; ++t) {
+        size_t lo = t * chunk;
+        size_t hi = lo + chunk < count ? lo + chunk : count;
+        if (lo >= hi) continue;
+        Fr cur = first * base.pow_u64((u64)lo);
+        for (size_t k = lo; k < hi; ++k) {
+            out[k] = cur;
+            cur = cur * base;
+        }
+    }
 }
 
 // Coset NTT: evaluate on {g * w^k} — multiply a[j] by g^j first.

@@ -5,9 +5,9 @@
 // in and out, matching the convention the CPU oracle pins (oracle/ntt.hpp).
 //
 // Structure (designed for gfx950, not a port):
-//  - n <= 4096:  one workgroup per transform, whole transform staged in LDS
-//    (4096 * 32 B = 128 KiB), DIT butterflies after a bit-reversed load.
-//  - n >= 8192:  four-step N = N1*N2 decomposition, two passes:
+//  - n <= 1024:  one workgroup per transform, whole transform staged in LDS
+//    (1024 * 32 B = 32 KiB), DIT butterflies after a bit-reversed load.
+//  - n >= 2048:  four-step N = N1*N2 decomposition, two passes:
 //      K1: column pairs (stride N1) -> length-N2 DFT in LDS -> outer twiddle
 //          w_N^(j1*k2) from two product tables (TA/TB, L2-resident) -> store.
 //      K2: row pairs (contiguous)   -> length-N1 DFT in LDS -> strided store
@@ -41,7 +41,7 @@ __global__ void k_pow_table(Fr* out, Fr base, uint64_t step, uint64_t count) {
     out[i] = base.pow_u64(e);
 }
 
-// ---- single-workgroup NTT (n <= 4096), one transform per block ----
+// ---- single-workgroup NTT (n <= 1024), one transform per block ----
 __global__ __launch_bounds__(512) void k_ntt_small(Fr* data, const Fr* wst,
                                                    uint32_t n, uint32_t logn,
                                                    Fr scale, int do_scale) {

@@ -291,6 +291,18 @@ static int build_pow_table(Fr** out, const Fr& base, uint64_t step, uint64_t cou
 // serial stages), so route n >= 2048 through the two-pass col/row path
 // (64-wide grids) — measured 3x faster at n=4096 (the proof domain).
 static constexpr uint32_t NTT_SMALL_MAX = 1024;
+// largest transform: the row pass stages N1 = 2^ceil(logn/2) elements in one
+// workgroup's LDS, and 2^24 (N1 = 4096, 128 KiB) is the last size whose row
+// fits the 160 KiB a workgroup has; 2^25 would ask for 256 KiB.  The
+// 128 KiB dynamic request is granted by the plain launch below
+// (tests/test_ntt_tiers.py compares 2^23 and 2^24 in full).
+static constexpr uint64_t NTT_MAX_N = 1ull << 24;
+
+// public-API argument contract (include/rng_prover.h), checked before any
+// allocation, copy or plan construction
+static bool ntt_args_ok(uint64_t n, uint64_t batch) {
+    return n >= 2 && !(n & (n - 1)) && n <= NTT_MAX_N && batch >= 1;
+}
 
 static NttPlan* get_plan(RngCtxImpl* ctx, uint32_t n, uint64_t batch) {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2413,8 +2425,7 @@ int rng_device_sync(void) {
 
 int rng_ntt_fr_dev(RngCtx* ctx, void* dev_data, uint64_t n, uint64_t batch, int inverse) {
     if (!gpu_ok()) return RNG_ERR_NO_GPU;
-    if (!ctx || !dev_data || n < 2 || (n & (n - 1)) || n > (1ull << 26))
-        return RNG_ERR_BAD_ARG;
+    if (!ctx || !dev_data || !ntt_args_ok(n, batch)) return RNG_ERR_BAD_ARG;
     Fr* data = (Fr*)dev_data;
     NttPlan* p = get_plan(&ctx->impl, (uint32_t)n, batch);
     if (!p) return RNG_ERR_HIP;
@@ -2429,14 +2440,15 @@ int rng_ntt_fr_dev(RngCtx* ctx, void* dev_data, uint64_t n, uint64_t batch, int 
 int rng_ntt_fr_dev_oop(RngCtx* ctx, void* dev_in, void* dev_out, uint64_t n,
                        uint64_t batch, int inverse) {
     if (!gpu_ok()) return RNG_ERR_NO_GPU;
-    if (!ctx || !dev_in || !dev_out || n < 2 || (n & (n - 1)) || n > (1ull << 26))
-        return RNG_ERR_BAD_ARG;
+    if (!ctx || !dev_in || !dev_out || !ntt_args_ok(n, batch)) return RNG_ERR_BAD_ARG;
+    // pass 2 reads contiguous rows and writes strided columns: aliasing races
+    if (n > NTT_SMALL_MAX && dev_in == dev_out) return RNG_ERR_BAD_ARG;
     return ntt_dev_run(&ctx->impl, (Fr*)dev_in, (Fr*)dev_out, (uint32_t)n, batch, inverse);
 }
 
 int rng_ntt_fr(RngCtx* ctx, uint64_t* data, uint64_t n, uint64_t batch, int inverse) {
     if (!gpu_ok()) return RNG_ERR_NO_GPU;
-    if (!ctx || !data || n < 2 || (n & (n - 1)) || n > (1ull << 26)) return RNG_ERR_BAD_ARG;
+    if (!ctx || !data || !ntt_args_ok(n, batch)) return RNG_ERR_BAD_ARG;
     size_t bytes = n * batch * sizeof(Fr);
     Fr* d = nullptr;
     HIP_CHECK(hipMalloc(&d, bytes));

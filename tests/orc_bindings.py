@@ -114,6 +114,27 @@ class OracleLib:
     def ntt(self, data_u64, n, inverse=False):
         self.lib.orc_ntt(ptr(data_u64), ctypes.c_uint64(n), ctypes.c_int(1 if inverse else 0))
 
+    def fr_poly_eval(self, coeffs_u64, n, points_u64):
+        """Horner evaluation of n Montgomery coefficients (4*n u64) at the
+        Montgomery points (4*npts u64).  Returns 4*npts u64."""
+        assert coeffs_u64.dtype == np.uint64 and coeffs_u64.size == 4 * n
+        assert points_u64.dtype == np.uint64 and points_u64.size % 4 == 0
+        npts = points_u64.size // 4
+        out = arr(4 * npts)
+        self.lib.orc_fr_poly_eval(ptr(coeffs_u64), ctypes.c_uint64(n), ptr(points_u64),
+                                  ctypes.c_uint64(npts), ptr(out))
+        return out
+
+    def fr_geom_table(self, first, base, count):
+        """out[k] = first * base^k for k < count; first and base are Python
+        ints holding Montgomery residues.  Returns 4*count u64."""
+        f, b = arr(4), arr(4)
+        f[:] = [(first >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+        b[:] = [(base >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+        out = arr(4 * count)
+        self.lib.orc_fr_geom_table(ptr(f), ptr(b), ctypes.c_uint64(count), ptr(out))
+        return out
+
     # MSM ------------------------------------------------------------------
     def msm(self, bases_u64, scalars_u64, n, window_c=13, naive=False):
         o = arr(9)

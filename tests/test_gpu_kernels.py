@@ -60,6 +60,33 @@ def mk_fr_mont(n, seed):
     return data
 
 
+def fr_add_limbs(a, b):
+    """(a + b) mod r over flat arrays of 4-limb residues below r, in numpy."""
+    a, b = a.reshape(-1, 4), b.reshape(-1, 4)
+    s = np.empty_like(a)
+    carry = np.zeros(a.shape[0], dtype=np.uint64)
+    for i in range(4):
+        t = a[:, i] + b[:, i]
+        c = t < a[:, i]
+        s[:, i] = t + carry
+        carry = (c | (s[:, i] < t)).astype(np.uint64)
+    # a, b < r < 2^254: no carry out of the top limb.  Subtract r where s >= r.
+    r = [np.uint64(l) for l in ref.int_to_limbs(ref.R)]
+    ge = np.ones(a.shape[0], dtype=bool)   # s >= r, decided from the top limb down
+    open_ = np.ones(a.shape[0], dtype=bool)
+    for i in (3, 2, 1, 0):
+        ge = np.where(open_ & (s[:, i] != r[i]), s[:, i] > r[i], ge)
+        open_ &= s[:, i] == r[i]
+    borrow = np.zeros(a.shape[0], dtype=np.uint64)
+    d = np.empty_like(s)
+    for i in range(4):
+        t = s[:, i] - r[i]
+        bo = s[:, i] < r[i]
+        d[:, i] = t - borrow
+        borrow = (bo | (t < borrow)).astype(np.uint64)
+    return np.where(ge[:, None], d, s).reshape(-1)
+
+
 class TestMsmGpu:
     def _bases(self, orc, g1, n, tile=True):
         """Take n bases from the SRS (repeat/tile if needed)."""
@@ -180,3 +207,6 @@ class TestNttGpu:
             vb = ref.limbs_to_int(b[4 * i:4 * i + 4])
             vs = ref.limbs_to_int(s[4 * i:4 * i + 4])
             assert (va + vb) % ref.R == vs
+        # and every slot: the outputs are arbitrary residues, so add them
+        # mod r limb by limb
+        assert np.array_equal(fr_add_limbs(a, b), s)

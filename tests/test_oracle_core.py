@@ -145,6 +145,89 @@ class TestNTT:
             vc = ref.from_mont(ref.limbs_to_int(fc[4 * i:4 * i + 4]), ref.R)
             assert va * vb % ref.R == vc, f"slot {i}"
 
+
+
+def test_fr_add_limbs_helper():
+    """The numpy mod-r add that test_linearity uses, against bignums,
+    including sums of exactly r, r - 1, r + 1 and limb-carry chains."""
+    from tests.test_gpu_kernels import fr_add_limbs
+    rng = random.Random(77)
+    pairs = [(0, 0), (ref.R - 1, 1), (ref.R - 1, 0), (ref.R - 1, 2), (ref.R - 1, ref.R - 1),
+             ((1 << 64) - 1, 1), ((1 << 192) - 1, 1), (ref.R >> 1, (ref.R >> 1) + 1)]
+    pairs += [(rand_fr(rng), rand_fr(rng)) for _ in range(200)]
+    a = np.array([l for x, _ in pairs for l in ref.int_to_limbs(x)], dtype=np.uint64)
+    b = np.array([l for _, y in pairs for l in ref.int_to_limbs(y)], dtype=np.uint64)
+    got = fr_add_limbs(a, b)
+    expect = [(x + y) % ref.R for x, y in pairs]
+    assert [ref.limbs_to_int(got[4 * i:4 * i + 4]) for i in range(len(pairs))] == expect
+
+
+class TestNttReferenceHelpers:
+    """fr_geom_table and fr_poly_eval against Python bignums.  They are the
+    reference for the GPU NTT above 2^20 (tests/test_ntt_tiers.py), where
+    orc.ntt is too slow, so they are pinned here first."""
+
+    @staticmethod
+    def _ints(a):
+        return [ref.limbs_to_int(a[4 * i:4 * i + 4]) for i in range(a.size // 4)]
+
+    # 1009 is prime: no thread count above one splits it into equal chunks
+    @pytest.mark.parametrize("count", [1, 2, 1000, 1009])
+    def test_geom_table(self, orc, count):
+        rng = random.Random(500 + count)
+        first, base = rand_fr(rng), rand_fr(rng)
+        got = orc.fr_geom_table(ref.to_mont(first, ref.R), ref.to_mont(base, ref.R), count)
+        expect = [ref.to_mont(first * pow(base, k, ref.R) % ref.R, ref.R)
+                  for k in range(count)]
+        assert self._ints(got) == expect
+
+    def test_geom_table_first_zero(self, orc):
+        base = rand_fr(random.Random(51))
+        got = orc.fr_geom_table(0, ref.to_mont(base, ref.R), 1000)
+        assert not got.any()
+
+    def test_geom_table_base_one(self, orc):
+        first = ref.to_mont(rand_fr(random.Random(52)), ref.R)
+        got = orc.fr_geom_table(first, ref.to_mont(1, ref.R), 1000)
+        assert self._ints(got) == [first] * 1000
+
+    def test_geom_table_root_of_unity_wraps(self, orc):
+        """base = w_64 over 130 entries: the table repeats with period 64."""
+        w = ref.fr_root_of_unity(64)
+        got = self._ints(orc.fr_geom_table(ref.to_mont(3, ref.R), ref.to_mont(w, ref.R), 130))
+        assert got[64:128] == got[:64] and got[128:] == got[:2]
+        assert len(set(got[:64])) == 64
+
+    @pytest.mark.parametrize("n,npts", [(1, 3), (2, 4), (37, 5)])
+    def test_poly_eval_vs_bignum(self, orc, n, npts):
+        rng = random.Random(600 + n)
+        coeffs = [rand_fr(rng) for _ in range(n)]
+        points = [0, 1, ref.R - 1][:npts] + [rand_fr(rng) for _ in range(max(0, npts - 3))]
+        c = np.array([l for v in coeffs for l in ref.int_to_limbs(ref.to_mont(v, ref.R))],
+                     dtype=np.uint64)
+        p = np.array([l for v in points for l in ref.int_to_limbs(ref.to_mont(v, ref.R))],
+                     dtype=np.uint64)
+        got = [ref.from_mont(v, ref.R) for v in self._ints(orc.fr_poly_eval(c, n, p))]
+        expect = [sum(a * pow(x, j, ref.R) for j, a in enumerate(coeffs)) % ref.R
+                  for x in points]
+        assert got == expect
+
+    def test_poly_eval_is_the_ntt(self, orc):
+        """poly_eval(a, w^k) == orc.ntt(a)[k] for every k at n = 64, with the
+        points themselves taken from fr_geom_table."""
+        n = 64
+        rng = random.Random(64)
+        a = np.array([l for _ in range(n)
+                      for l in ref.int_to_limbs(ref.to_mont(rand_fr(rng), ref.R))],
+                     dtype=np.uint64)
+        w = ref.fr_root_of_unity(n)
+        points = orc.fr_geom_table(ref.to_mont(1, ref.R), ref.to_mont(w, ref.R), n)
+        got = orc.fr_poly_eval(a, n, points)
+        expect = a.copy()
+        orc.ntt(expect, n)
+        assert np.array_equal(got, expect)
+
+
 class TestMSM:
     def _mk(self, orc, n, seed):
         rng = random.Random(seed)
