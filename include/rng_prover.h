@@ -162,6 +162,22 @@ int rng_perm_product(RngCtx* ctx, const uint64_t* wires, const uint64_t* sigma_e
                      const uint64_t* k5, const uint64_t* beta_gamma,
                      uint64_t n, uint64_t batch, uint64_t* out_z);
 
+/* Batched Horner scan on the GPU (rounds 4 and 5 of the prover).  For a
+ * coefficient sequence c[0..len) and a point x let
+ *   S[i] = sum_{j>=i} c[j] x^(j-i),   i.e.  S[i] = c[i] + x S[i+1].
+ * mode 0 (evaluate): out = S[0] = c(x) per sequence, batch x group Fr.
+ * mode 1 (divide):   out = S[1..len-1] per sequence, batch x group x (len-1)
+ *                    Fr: the quotient of c(X) by (X - x), remainder dropped.
+ * No inverse of x is taken, so x = 0 and x = 1 are ordinary points.
+ * Sequences are addressed as batch x group: item b has one point, points[b],
+ * shared by its `group` polynomials; polys = batch x group x len Fr, or
+ * group x len Fr shared by every item when shared != 0.
+ * host buffers, Montgomery Fr.  1 <= len <= 2^17 + 3 (len >= 2 in mode 1),
+ * group >= 1, batch >= 1, batch * group <= 640. */
+int rng_poly_horner(RngCtx* ctx, const uint64_t* polys, uint64_t len, uint64_t group,
+                    uint64_t batch, int shared, const uint64_t* points, int mode,
+                    uint64_t* out);
+
 /* Device buffer helpers */
 void* rng_dbuf_alloc(size_t bytes);
 void rng_dbuf_free(void* dbuf);
@@ -221,6 +237,23 @@ int rng_prove_cohort(RngCtx* ctx, const RngProvingKey* pk, uint64_t k,
 int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wires,
                         const uint64_t* beta_gamma, uint64_t batch, int mode,
                         uint64_t* out_z);
+
+/* Test hook in the style of rng_perm_product_pk: the SAME internal call the
+ * provers' rounds 4 and 5 make once the 29 scalars of the batched opening
+ * are known, against the key's own selector and sigma coefficients (n = the
+ * key's domain size).  Per proof p:
+ *   C_p      = sum_t scalars[p][t] * P_t   (13 selectors, sigma_0..3, sigma_4,
+ *              wires 0..4, z, chunks 0..4: the order of open_scalars)
+ *   W_zeta   = C_p / (X - points[p][0]),   W_zeta_w = z_p / (X - points[p][1])
+ * host buffers, Montgomery Fr; polys = k x 11 x (n+3): wires 0..4 (n+2
+ * coefficients), z (n+3), chunks 0..3 (n+3), chunk 4 (n+2), each zero-padded
+ * to n+3; points = k x 2; scalars = k x 29; out_w = k x 2 x (n+2): W_zeta
+ * then W_zeta_w of each proof.  1 <= k <= 128.
+ * mode 0 = what the prover would pick (RNG_OPEN_DEVICE, else the per-path
+ * default; k = 1 is the single-proof path), 1 = device, 2 = host loops. */
+int rng_open_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t* polys,
+                const uint64_t* points, const uint64_t* scalars, int mode,
+                uint64_t* out_w);
 
 int rng_verify(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* public_inputs,
                const uint64_t* proof);

@@ -222,6 +222,21 @@ __global__ __launch_bounds__(256) void k_copy_pad_batch(const Fr* src, uint32_t 
     dst[i] = (j < len) ? src[b * len + j] : Fr::zero();
 }
 
+// k_mul_pointwise_mod and k_copy_pad_batch in one out-of-place pass: nb
+// polys of `len` coefficients in src, scaled by table[j], padded to m in
+// dst.  src keeps the plain coefficients (rounds 4 and 5 on the device read
+// them again).
+__global__ __launch_bounds__(256) void k_scale_pad_batch(const Fr* src, uint32_t len,
+                                                         const Fr* table, Fr* dst,
+                                                         uint32_t m,
+                                                         uint64_t total /* nb*m */) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    uint64_t b = i / m;
+    uint32_t j = (uint32_t)(i - b * m);
+    dst[i] = (j < len) ? src[b * len + j].mul(table[j]) : Fr::zero();
+}
+
 // ---- field-mul microbenchmark kernels (A/B the Montgomery formulations) ----
 // Each thread runs `iters` muls: dep = a dependent chain (latency),
 // otherwise 4 independent chains (throughput).

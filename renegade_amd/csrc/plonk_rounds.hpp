@@ -181,41 +181,83 @@ inline LinScalars lin_scalars(const Fr k[5], uint64_t n, const Fr wb[5], const F
     return s;
 }
 
-// R4 + R5 of one proof: evaluations at zeta into the state and the
-// transcript, v, the linearization D, the batched opening C, and the two
+// ---- R4 + R5 in three pieces, shared by the host path (rounds_4_5) and the
+// device stage (open_dev in prover_api.hip) ----
+
+// Piece 1: the ten evaluations already in the state go into the transcript
+// (wires, sigma_0..3, z at zeta*w) and v is drawn.
+inline void absorb_evals(ProofState& st) {
+    for (int j = 0; j < 5; ++j) st.tr.append_fr(st.wire_evals[j]);
+    for (int j = 0; j < 4; ++j) st.tr.append_fr(st.sigma_evals[j]);
+    st.tr.append_fr(st.z_shift_eval);
+    st.v = st.tr.challenge();
+}
+
+// Piece 2: the scalars of the batched opening C = D + sum v^i (opened
+// polynomial i).  This is the one place that fixes the order of the 29
+// polynomials, for the host loops below and for k_open_lincomb:
+//   0..12  selectors            17      sigma_4        23      z
+//   13..16 sigma_0..3 (v^6..9)  18..22  wires (v^1..5) 24..28  quotient chunks
+enum : int {
+    OPEN_SEL = 0,
+    OPEN_SIGMA = 13,
+    OPEN_WIRES = 18,
+    OPEN_Z = 23,
+    OPEN_CHUNKS = 24,
+    OPEN_COUNT = 29,
+    OPEN_PROOF_POLYS = 11,  // per proof: wires 0..4, z, chunks 0..4
+};
+
+inline void open_scalars(const LinScalars& ls, const Fr& v, Fr out[OPEN_COUNT]) {
+    for (int i = 0; i < 13; ++i) out[OPEN_SEL + i] = ls.sel[i];
+    Fr vp = Fr::one();
+    for (int j = 0; j < 5; ++j) {
+        vp = vp.mul(v);
+        out[OPEN_WIRES + j] = vp;
+    }
+    for (int j = 0; j < 4; ++j) {
+        vp = vp.mul(v);
+        out[OPEN_SIGMA + j] = vp;
+    }
+    out[OPEN_SIGMA + 4] = ls.sigma4;
+    out[OPEN_Z] = ls.z;
+    for (int i = 0; i < 5; ++i) out[OPEN_CHUNKS + i] = ls.chunk[i];
+}
+
+// Piece 3, host form: C from the 29 scalars, then the two opening
+// quotients.  polys = the proof's own 11 polynomials (wires 0..4, z, chunks
+// 0..4); the other 18 are the key's.
+inline void open_host(const PlonkPkHost& pk, const std::vector<Fr>* const polys[OPEN_PROOF_POLYS],
+                      const Fr s[OPEN_COUNT], const Fr& zeta, const Fr& zeta_w,
+                      std::vector<Fr>& Wz, std::vector<Fr>& Wzw) {
+    std::vector<Fr> C;
+    for (int i = 0; i < 13; ++i) hpoly_add_scaled(C, pk.selq[i], s[OPEN_SEL + i]);
+    for (int j = 0; j < 5; ++j) hpoly_add_scaled(C, pk.sigp[j], s[OPEN_SIGMA + j]);
+    for (int j = 0; j < OPEN_PROOF_POLYS; ++j) hpoly_add_scaled(C, *polys[j], s[OPEN_WIRES + j]);
+    Wz = hpoly_div_linear(C, zeta);
+    Wzw = hpoly_div_linear(*polys[5], zeta_w);
+}
+
+// R4 + R5 of one proof on the host: evaluations at zeta into the state and
+// the transcript, v, the linearization D, the batched opening C, and the two
 // opening quotients.  w = the n-th root of unity of the proof domain.
 inline void rounds_4_5(const PlonkPkHost& pk, const Fr& w, ProofState& st,
                        std::vector<Fr>& Wz, std::vector<Fr>& Wzw) {
-    for (int j = 0; j < 5; ++j) {
-        st.wire_evals[j] = hpoly_eval(st.wpoly[j], st.zeta);
-        st.tr.append_fr(st.wire_evals[j]);
-    }
-    for (int j = 0; j < 4; ++j) {
-        st.sigma_evals[j] = hpoly_eval(pk.sigp[j], st.zeta);
-        st.tr.append_fr(st.sigma_evals[j]);
-    }
-    st.z_shift_eval = hpoly_eval(st.zpoly, st.zeta.mul(w));
-    st.tr.append_fr(st.z_shift_eval);
-    st.v = st.tr.challenge();
+    const Fr zeta_w = st.zeta.mul(w);
+    for (int j = 0; j < 5; ++j) st.wire_evals[j] = hpoly_eval(st.wpoly[j], st.zeta);
+    for (int j = 0; j < 4; ++j) st.sigma_evals[j] = hpoly_eval(pk.sigp[j], st.zeta);
+    st.z_shift_eval = hpoly_eval(st.zpoly, zeta_w);
+    absorb_evals(st);
 
     const LinScalars ls = lin_scalars(pk.k, pk.n, st.wire_evals, st.sigma_evals,
                                       st.z_shift_eval, st.beta, st.gamma, st.alpha, st.zeta);
-    std::vector<Fr> C;  // D, then the v-powers of the opened polynomials
-    for (int i = 0; i < 13; ++i) hpoly_add_scaled(C, pk.selq[i], ls.sel[i]);
-    hpoly_add_scaled(C, st.zpoly, ls.z);
-    hpoly_add_scaled(C, pk.sigp[4], ls.sigma4);
-    for (int i = 0; i < 5; ++i) hpoly_add_scaled(C, st.quot_chunks[i], ls.chunk[i]);
-    Fr vp = Fr::one();
-    for (int j = 0; j < 5; ++j) {
-        vp = vp.mul(st.v);
-        hpoly_add_scaled(C, st.wpoly[j], vp);
-    }
-    for (int j = 0; j < 4; ++j) {
-        vp = vp.mul(st.v);
-        hpoly_add_scaled(C, pk.sigp[j], vp);
-    }
-    Wz = hpoly_div_linear(C, st.zeta);
-    Wzw = hpoly_div_linear(st.zpoly, st.zeta.mul(w));
+    Fr s[OPEN_COUNT];
+    open_scalars(ls, st.v, s);
+    const std::vector<Fr>* polys[OPEN_PROOF_POLYS] = {
+        &st.wpoly[0], &st.wpoly[1], &st.wpoly[2], &st.wpoly[3], &st.wpoly[4], &st.zpoly,
+        &st.quot_chunks[0], &st.quot_chunks[1], &st.quot_chunks[2], &st.quot_chunks[3],
+        &st.quot_chunks[4]};
+    open_host(pk, polys, s, st.zeta, zeta_w, Wz, Wzw);
 }
 
 }  // namespace rng

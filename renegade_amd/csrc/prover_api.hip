@@ -31,6 +31,7 @@
 #include "lagrange_kernels.hip"
 #include "plonk_kernels.hip"
 #include "perm_kernels.hip"
+#include "open_kernels.hip"
 #include "plonk_circuit.hpp"
 #include "plonk_host.hpp"
 #include "plonk_rounds.hpp"
@@ -443,12 +444,13 @@ static const MsmEnv& msm_env() {
     return env;
 }
 
-// The prover's own switches, read once per process.  z_device and
-// r1_lagrange: -1 = unset (the per-path *_DEFAULT_* constants decide), 0 =
+// The prover's own switches, read once per process.  z_device, r1_lagrange
+// and open_device: -1 = unset (the per-path *_DEFAULT_* constants decide), 0 =
 // off, 1 = on in both provers.
 struct ProverEnv {
     int z_device;      // RNG_Z_DEVICE: R2 grand product on the device
     int r1_lagrange;   // RNG_R1_LAGRANGE: R1 commits in the Lagrange basis
+    int open_device;   // RNG_OPEN_DEVICE: R4 + R5 on the device
     int cohort_trace;  // RNG_COHORT_TRACE: stderr timeline of a cohort
     static bool on(int v, bool path_default) { return v < 0 ? path_default : v == 1; }
 };
@@ -460,7 +462,8 @@ static const ProverEnv& prover_env() {
             return e ? (atoi(e) != 0 ? 1 : 0) : -1;
         };
         const char* t = getenv("RNG_COHORT_TRACE");
-        return ProverEnv{tri("RNG_Z_DEVICE"), tri("RNG_R1_LAGRANGE"), t ? atoi(t) : 0};
+        return ProverEnv{tri("RNG_Z_DEVICE"), tri("RNG_R1_LAGRANGE"), tri("RNG_OPEN_DEVICE"),
+                         t ? atoi(t) : 0};
     }();
     return env;
 }
@@ -1191,10 +1194,11 @@ struct PlonkPkImpl : PlonkPkHost {  // host half: plonk_rounds.hpp
     Fr* l1_coset = nullptr;    // device m
     Fr* sig_evals_dev = nullptr;  // device 5*n (grand-product stage)
     Fr* wpow_dev = nullptr;       // device n: w^t
+    Fr* coef_dev = nullptr;       // device 18*n: selq[0..12], sigp[0..4] (R4 + R5 stage)
     RngCtxImpl* ctx = nullptr;
     ~PlonkPkImpl() {
         for (void* b : {(void*)sel_coset, (void*)sig_coset, (void*)l1_coset,
-                        (void*)sig_evals_dev, (void*)wpow_dev})
+                        (void*)sig_evals_dev, (void*)wpow_dev, (void*)coef_dev})
             hip_free_guarded(b);
     }
 };
@@ -1378,6 +1382,201 @@ static int commit_dev(RngCtxImpl* ctx, const std::vector<Fr>& coeffs, G1Aff* out
                       bool* out_inf) {
     const std::vector<Fr>* p = &coeffs;
     return commit_dev_batch(ctx, &p, 1, out, out_inf);
+}
+
+// ---------------- R4 + R5: evaluations, linearization, openings ----------------
+
+// RNG_OPEN_DEVICE (ProverEnv::open_device): 0 = the host rounds
+// (rounds_4_5), 1 = the device stage (open_kernels.hip) in both provers.
+// Unset: per-path defaults below, set by the A/B measurement in DESIGN.md
+// §4.5 (profiles/open_device_ab.json).
+constexpr bool OPEN_DEVICE_DEFAULT_SINGLE = true;
+constexpr bool OPEN_DEVICE_DEFAULT_COHORT = true;
+static_assert(OPEN_TERMS == OPEN_COUNT, "k_open_lincomb follows open_scalars");
+
+// the ten evaluations of every proof of a full cohort, and any one call
+constexpr size_t OPEN_MAX_EVALS = 10 * (size_t)OPEN_MAX_BATCH;
+static_assert(OPEN_MAX_EVALS >= OPEN_MAX_SEQ, "one call's results fit");
+
+struct OpenScratch {  // per-thread small buffers of the device stage (~2.7 MiB)
+    Fr* dev = nullptr;      // one allocation, carved below
+    Fr* tile_io = nullptr;  // OPEN_MAX_SEQ * OPEN_MAX_TILES tile totals / carries
+    Fr* pts = nullptr;      // OPEN_MAX_SEQ points (the provers: k x (zeta, zeta*w))
+    Fr* evals = nullptr;    // OPEN_MAX_EVALS reduce-mode results
+    Fr* scal = nullptr;     // OPEN_MAX_BATCH x 29 scalars
+    std::vector<Fr> h_up, h_evals;  // host staging (outlives the async copies)
+    ~OpenScratch() { hip_free_guarded(dev); }
+};
+
+static thread_local std::unique_ptr<OpenScratch> tls_open_scratch;
+
+static OpenScratch* open_scratch_get() {
+    if (tls_open_scratch) return tls_open_scratch.get();
+    auto s = std::make_unique<OpenScratch>();
+    const size_t tiles = (size_t)OPEN_MAX_SEQ * OPEN_MAX_TILES;
+    const size_t elems =
+        tiles + OPEN_MAX_SEQ + OPEN_MAX_EVALS + (size_t)OPEN_MAX_BATCH * OPEN_TERMS;
+    if (hipMalloc(&s->dev, elems * sizeof(Fr)) != hipSuccess) return nullptr;
+    s->tile_io = s->dev;
+    s->pts = s->tile_io + tiles;
+    s->evals = s->pts + OPEN_MAX_SEQ;
+    s->scal = s->evals + OPEN_MAX_EVALS;
+    s->h_up.resize((size_t)OPEN_MAX_BATCH * (2 + OPEN_TERMS));
+    s->h_evals.resize(OPEN_MAX_EVALS);
+    tls_open_scratch = std::move(s);
+    return tls_open_scratch.get();
+}
+
+static bool open_shape_ok(uint64_t len, uint64_t group, uint64_t batch, int mode) {
+    return len >= (mode == 1 ? 2u : 1u) && len <= OPEN_MAX_LEN && group >= 1 && batch >= 1 &&
+           group <= OPEN_MAX_SEQ && batch <= OPEN_MAX_SEQ && group * batch <= OPEN_MAX_SEQ &&
+           (mode == 0 || mode == 1);
+}
+
+// One batched Horner call on RNG_STREAM, all pointers on the device.  mode 0
+// (reduce): evals[b*group + g] = the evaluation.  mode 1 (scan): q.out gets
+// the len - 1 quotient coefficients of every sequence.  q.tiles is set here.
+static int horner_dev(OpenScratch* os, OpenSeqs q, uint32_t batch, int mode, Fr* evals) {
+    if (!open_shape_ok(q.len, q.group, batch, mode)) return RNG_ERR_BAD_ARG;
+    const uint32_t nseq = batch * q.group;
+    q.tiles = (q.len + OPEN_TILE - 1) / OPEN_TILE;
+    if (q.tiles == 1) {
+        if (mode == 0)
+            hipLaunchKernelGGL((k_open_horner_tile<false, false>), dim3(nseq), dim3(OPEN_WG),
+                               0, RNG_STREAM, q, evals);
+        else
+            hipLaunchKernelGGL((k_open_horner_tile<false, true>), dim3(nseq), dim3(OPEN_WG),
+                               0, RNG_STREAM, q, (Fr*)nullptr);
+        HIP_CHECK(hipGetLastError());
+        return RNG_OK;
+    }
+    hipLaunchKernelGGL((k_open_horner_tile<false, false>), dim3(nseq * q.tiles),
+                       dim3(OPEN_WG), 0, RNG_STREAM, q, os->tile_io);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_open_tile_prefix, dim3(nseq), dim3(OPEN_WG), 0, RNG_STREAM, q.pts,
+                       q.pt_stride, q.group, q.tiles, os->tile_io,
+                       mode == 0 ? evals : (Fr*)nullptr);
+    HIP_CHECK(hipGetLastError());
+    if (mode == 1) {
+        hipLaunchKernelGGL((k_open_horner_tile<true, true>), dim3(nseq * q.tiles),
+                           dim3(OPEN_WG), 0, RNG_STREAM, q, os->tile_io);
+        HIP_CHECK(hipGetLastError());
+    }
+    return RNG_OK;
+}
+
+// Where the 11 polynomials of each of k proofs are on the device: wires 0..4
+// and z as six slots of stride n + 3 per proof, the chunks as five.
+struct OpenSrc {
+    const Fr* wz;
+    uint64_t wz_item;
+    const Fr* chunks;
+    uint64_t ch_item;
+};
+
+// Steps 1-3: the ten evaluations of every proof.  points = k x (zeta,
+// zeta*w) on the host; on return (stream synchronized) os->h_evals holds
+// 5k wire evaluations, then 4k sigma, then k of z.
+static int open_evals_dev(const PlonkPkImpl& pk, const OpenSrc& src, uint32_t k,
+                          const Fr* points, OpenScratch* os) {
+    const uint32_t n = (uint32_t)pk.n;
+    memcpy(os->h_up.data(), points, 2 * (size_t)k * sizeof(Fr));
+    HIP_CHECK(hipMemcpyAsync(os->pts, os->h_up.data(), 2 * (size_t)k * sizeof(Fr),
+                             hipMemcpyHostToDevice, RNG_STREAM));
+    OpenSeqs q{};
+    q.pts = os->pts;
+    q.pt_stride = 2;
+    q.src = src.wz, q.item_stride = src.wz_item, q.poly_stride = (uint64_t)n + 3;
+    q.len = n + 2, q.group = 5;
+    int rc = horner_dev(os, q, k, 0, os->evals);
+    if (rc != RNG_OK) return rc;
+    q.src = pk.coef_dev + 13 * (size_t)n, q.item_stride = 0, q.poly_stride = n;
+    q.len = n, q.group = 4;
+    rc = horner_dev(os, q, k, 0, os->evals + 5 * (size_t)k);
+    if (rc != RNG_OK) return rc;
+    q.pts = os->pts + 1;
+    q.src = src.wz + 5 * ((size_t)n + 3), q.item_stride = src.wz_item;
+    q.len = n + 3, q.group = 1;
+    rc = horner_dev(os, q, k, 0, os->evals + 9 * (size_t)k);
+    if (rc != RNG_OK) return rc;
+    HIP_CHECK(hipMemcpyAsync(os->h_evals.data(), os->evals, 10 * (size_t)k * sizeof(Fr),
+                             hipMemcpyDeviceToHost, RNG_STREAM));
+    HIP_CHECK(hipStreamSynchronize(RNG_STREAM));
+    return RNG_OK;
+}
+
+// Steps 5-7: C_p from the 29 scalars of each proof (into C, k x (n + 3)),
+// then W_zeta = C_p / (X - zeta_p) and W_zeta_w = z_p / (X - zeta_p w) as two
+// consecutive (n + 2)-coefficient blocks per proof in W.  points and scalars
+// on the host; C and W on the device, neither aliasing a source.
+static int open_combine_dev(const PlonkPkImpl& pk, const OpenSrc& src, uint32_t k,
+                            const Fr* points, const Fr* scalars, Fr* C, Fr* W) {
+    if (k < 1 || k > OPEN_MAX_BATCH || pk.n > OPEN_MAX_N) return RNG_ERR_BAD_ARG;
+    OpenScratch* os = open_scratch_get();
+    if (!os) return RNG_ERR_HIP;
+    const uint32_t n = (uint32_t)pk.n;
+    const size_t npts = 2 * (size_t)k, nsc = (size_t)OPEN_TERMS * k;
+    memcpy(os->h_up.data(), points, npts * sizeof(Fr));
+    memcpy(os->h_up.data() + npts, scalars, nsc * sizeof(Fr));
+    HIP_CHECK(hipMemcpyAsync(os->pts, os->h_up.data(), npts * sizeof(Fr),
+                             hipMemcpyHostToDevice, RNG_STREAM));
+    HIP_CHECK(hipMemcpyAsync(os->scal, os->h_up.data() + npts, nsc * sizeof(Fr),
+                             hipMemcpyHostToDevice, RNG_STREAM));
+    OpenPolys P{pk.coef_dev, src.wz, src.wz_item, src.chunks, src.ch_item};
+    hipLaunchKernelGGL(k_open_lincomb, dim3((n + 3 + 255) / 256, k), dim3(256), 0, RNG_STREAM,
+                       P, (const Fr*)os->scal, C, n);
+    HIP_CHECK(hipGetLastError());
+    OpenSeqs q{};
+    q.pts = os->pts;
+    q.pt_stride = 2;
+    q.src = C, q.item_stride = (uint64_t)n + 3;
+    q.len = n + 3, q.group = 1;
+    q.out = W, q.out_item_stride = 2 * ((uint64_t)n + 2);
+    int rc = horner_dev(os, q, k, 1, nullptr);
+    if (rc != RNG_OK) return rc;
+    q.pts = os->pts + 1;
+    q.src = src.wz + 5 * ((size_t)n + 3), q.item_stride = src.wz_item;
+    q.out = W + ((size_t)n + 2);
+    return horner_dev(os, q, k, 1, nullptr);
+}
+
+// The device stage of R4 + R5 for k proofs (st[0..k), zeta drawn): fills the
+// evaluations and v of every state and leaves W_zeta, W_zeta_w of proof p in
+// W blocks 2p, 2p + 1 for the caller's commit.  One stream sync, after the
+// evaluations: the transcript and the linearization scalars are host work
+// (on the pool for a cohort).
+static int open_dev(const PlonkPkImpl& pk, const Fr& w, const OpenSrc& src, uint32_t k,
+                    ProofState* st, Fr* C, Fr* W) {
+    if (k < 1 || k > OPEN_MAX_BATCH || pk.n > OPEN_MAX_N) return RNG_ERR_BAD_ARG;
+    OpenScratch* os = open_scratch_get();
+    if (!os) return RNG_ERR_HIP;
+    if (prover_env().cohort_trace || msm_env().debug) {
+        fprintf(stderr, "[open_dev] n=%llu k=%u device stage\n", (unsigned long long)pk.n, k);
+        fflush(stderr);
+    }
+    std::vector<Fr> points(2 * (size_t)k), scalars((size_t)OPEN_TERMS * k);
+    for (uint32_t p = 0; p < k; ++p) {
+        points[2 * (size_t)p] = st[p].zeta;
+        points[2 * (size_t)p + 1] = st[p].zeta.mul(w);
+    }
+    int rc = open_evals_dev(pk, src, k, points.data(), os);
+    if (rc != RNG_OK) return rc;
+    const Fr* ev = os->h_evals.data();
+    auto one = [&](uint32_t p) {
+        ProofState& s = st[p];
+        for (int j = 0; j < 5; ++j) s.wire_evals[j] = ev[5 * (size_t)p + j];
+        for (int j = 0; j < 4; ++j) s.sigma_evals[j] = ev[5 * (size_t)k + 4 * (size_t)p + j];
+        s.z_shift_eval = ev[9 * (size_t)k + p];
+        absorb_evals(s);
+        const LinScalars ls = lin_scalars(pk.k, pk.n, s.wire_evals, s.sigma_evals,
+                                          s.z_shift_eval, s.beta, s.gamma, s.alpha, s.zeta);
+        open_scalars(ls, s.v, scalars.data() + (size_t)OPEN_TERMS * p);
+    };
+    if (k > 1)
+        HostPool::inst().parallel_for(k, one);
+    else
+        one(0);
+    return open_combine_dev(pk, src, k, points.data(), scalars.data(), C, W);
 }
 
 // ---------------- cohort proving ----------------
@@ -1576,6 +1775,12 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     Fr w = h_fr_root_of_unity((uint32_t)n);
     const bool z_dev =
         ProverEnv::on(prover_env().z_device, Z_DEVICE_DEFAULT_COHORT) && n <= PERM_MAX_N;
+    // R4 + R5 on the device: the blinded polynomials stay on the device (the
+    // wires and z as plain coefficients in coset_in, the chunks in stage) and
+    // only wire 0 comes down, for a link hint
+    const bool open_on =
+        ProverEnv::on(prover_env().open_device, OPEN_DEVICE_DEFAULT_COHORT) &&
+        n <= OPEN_MAX_N;
 
     std::vector<ProofState> st;
     st.reserve(k);
@@ -1642,9 +1847,14 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
                            cs->coset_in, (uint32_t)n, total1);
         HIP_CHECK(hipGetLastError());
         uint64_t wlen = 5 * (uint64_t)k * (n + 2);
-        std::vector<Fr> host_flat(wlen);
-        HIP_CHECK(hipMemcpyAsync(host_flat.data(), cs->stage, wlen * sizeof(Fr),
-                                 hipMemcpyDeviceToHost, RNG_STREAM));
+        std::vector<Fr> host_flat(open_on ? (out_hints ? (size_t)k * (n + 2) : 0) : wlen);
+        if (!open_on)
+            HIP_CHECK(hipMemcpyAsync(host_flat.data(), cs->stage, wlen * sizeof(Fr),
+                                     hipMemcpyDeviceToHost, RNG_STREAM));
+        else if (out_hints)  // wire 0 of every proof: one row in five
+            HIP_CHECK(hipMemcpy2DAsync(host_flat.data(), (n + 2) * sizeof(Fr), cs->stage,
+                                       5 * (n + 2) * sizeof(Fr), (n + 2) * sizeof(Fr), k,
+                                       hipMemcpyDeviceToHost, RNG_STREAM));
         COHORT_TRACE("r1-sync-done");
         int crc = lagrange ? commit_lagrange_canon(ctx, n, cs->canon, 5 * k, cbuf.data(),
                                                    ibuf.get())
@@ -1653,6 +1863,13 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
             crc = commit_staged(ctx, n + 2, 5 * k, cbuf.data(), ibuf.get());
         if (crc != RNG_OK) return RNG_ERR_HIP;
         pool.parallel_for(k, [&](uint32_t p) {
+            if (open_on) {
+                if (out_hints) {
+                    const Fr* src = host_flat.data() + (size_t)p * (n + 2);
+                    st[p].wpoly[0].assign(src, src + (n + 2));
+                }
+                return;
+            }
             for (int j = 0; j < 5; ++j) {
                 const Fr* src = host_flat.data() + ((size_t)5 * p + j) * (n + 2);
                 st[p].wpoly[j].assign(src, src + (n + 2));
@@ -1721,15 +1938,18 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
                            cs->ntt_tmp + (size_t)k * n, cs->coset_in, (uint32_t)n,
                            totz);
         HIP_CHECK(hipGetLastError());
-        std::vector<Fr> z_host(totz);
-        HIP_CHECK(hipMemcpyAsync(z_host.data(), cs->stage, totz * sizeof(Fr),
-                                 hipMemcpyDeviceToHost, RNG_STREAM));
+        std::vector<Fr> z_host(open_on ? 0 : totz);
+        if (!open_on)
+            HIP_CHECK(hipMemcpyAsync(z_host.data(), cs->stage, totz * sizeof(Fr),
+                                     hipMemcpyDeviceToHost, RNG_STREAM));
         if (commit_staged(ctx, n + 3, k, cbuf.data(), ibuf.get()) != RNG_OK)
             return RNG_ERR_HIP;
         // commit_staged synchronized: z_host is complete
         pool.parallel_for(k, [&](uint32_t p) {
-            const Fr* src = z_host.data() + (size_t)p * (n + 3);
-            st[p].zpoly.assign(src, src + (n + 3));
+            if (!open_on) {
+                const Fr* src = z_host.data() + (size_t)p * (n + 3);
+                st[p].zpoly.assign(src, src + (n + 3));
+            }
             st[p].take_comms(COMM_Z, 1, &cbuf[p], &ibuf[p]);
             st[p].alpha = st[p].tr.challenge();
         });
@@ -1742,16 +1962,26 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         if (!mp || ensure_coset_tables(ctx, mp) != RNG_OK) return RNG_ERR_HIP;
         const uint64_t stride = n + 3;
         uint64_t total_in = 7 * (uint64_t)k * stride;
-        hipLaunchKernelGGL(k_mul_pointwise_mod,
-                           dim3((uint32_t)((total_in + 255) / 256)), dim3(256), 0,
-                           RNG_STREAM, cs->coset_in, mp->gpow, (uint32_t)stride,
-                           total_in);
-        HIP_CHECK(hipGetLastError());
         uint64_t total_m = 7 * (uint64_t)k * m;
-        hipLaunchKernelGGL(k_copy_pad_batch, dim3((uint32_t)((total_m + 255) / 256)),
-                           dim3(256), 0, RNG_STREAM, cs->coset_in, (uint32_t)stride,
-                           cs->ntt_tmp, m, total_m);
-        HIP_CHECK(hipGetLastError());
+        if (open_on) {
+            // R4 + R5 read the plain coefficients again: scale while padding,
+            // out of place
+            hipLaunchKernelGGL(k_scale_pad_batch, dim3((uint32_t)((total_m + 255) / 256)),
+                               dim3(256), 0, RNG_STREAM, (const Fr*)cs->coset_in,
+                               (uint32_t)stride, (const Fr*)mp->gpow, cs->ntt_tmp, m,
+                               total_m);
+            HIP_CHECK(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(k_mul_pointwise_mod,
+                               dim3((uint32_t)((total_in + 255) / 256)), dim3(256), 0,
+                               RNG_STREAM, cs->coset_in, mp->gpow, (uint32_t)stride,
+                               total_in);
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_copy_pad_batch, dim3((uint32_t)((total_m + 255) / 256)),
+                               dim3(256), 0, RNG_STREAM, cs->coset_in, (uint32_t)stride,
+                               cs->ntt_tmp, m, total_m);
+            HIP_CHECK(hipGetLastError());
+        }
         int rc = ntt_dev_run(ctx, cs->ntt_tmp, cs->coset_out, m, 7 * (uint64_t)k, false,
                              RNG_STREAM);
         if (rc != RNG_OK) return rc;
@@ -1793,18 +2023,20 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
                            RNG_STREAM, cs->ntt_tmp, cs->blinders, cs->stage,
                            (uint32_t)n, m, total_c);
         HIP_CHECK(hipGetLastError());
-        std::vector<Fr> chunks_host(total_c);
-        HIP_CHECK(hipMemcpyAsync(chunks_host.data(), cs->stage,
-                                 total_c * sizeof(Fr), hipMemcpyDeviceToHost,
-                                 RNG_STREAM));
+        std::vector<Fr> chunks_host(open_on ? 0 : total_c);
+        if (!open_on)
+            HIP_CHECK(hipMemcpyAsync(chunks_host.data(), cs->stage,
+                                     total_c * sizeof(Fr), hipMemcpyDeviceToHost,
+                                     RNG_STREAM));
         if (commit_staged(ctx, n + 3, 5 * k, cbuf.data(), ibuf.get()) != RNG_OK)
             return RNG_ERR_HIP;
-        pool.parallel_for(k, [&](uint32_t p) {
-            for (int i = 0; i < 5; ++i) {
-                const Fr* src = chunks_host.data() + (5 * (size_t)p + i) * (n + 3);
-                st[p].quot_chunks[i].assign(src, src + (i < 4 ? n + 3 : n + 2));
-            }
-        });
+        if (!open_on)
+            pool.parallel_for(k, [&](uint32_t p) {
+                for (int i = 0; i < 5; ++i) {
+                    const Fr* src = chunks_host.data() + (5 * (size_t)p + i) * (n + 3);
+                    st[p].quot_chunks[i].assign(src, src + (i < 4 ? n + 3 : n + 2));
+                }
+            });
         pool.parallel_for(k, [&](uint32_t p) {
             st[p].take_comms(COMM_CHUNKS, 5, &cbuf[5 * (size_t)p], &ibuf[5 * (size_t)p]);
             st[p].zeta = st[p].tr.challenge();
@@ -1812,15 +2044,30 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     }
 
     COHORT_TRACE("r4r5");
-    // --- R4 + R5: evaluations, linearization, openings (host pool) ---
-    std::vector<std::vector<Fr>> Wz(k), Wzw(k);
-    pool.parallel_for(k, [&](uint32_t p) { rounds_4_5(pk, w, st[p], Wz[p], Wzw[p]); });
-    for (uint32_t p = 0; p < k; ++p) {
-        ps[2 * (size_t)p] = &Wz[p];
-        ps[2 * (size_t)p + 1] = &Wzw[p];
+    // --- R4 + R5: evaluations, linearization, openings (device stage or
+    //     host pool) ---
+    if (open_on) {
+        // coset_out, q_all and ntt_tmp are free after the chunk split: C goes
+        // to q_all, W_zeta / W_zeta_w to ntt_tmp, and the commit reads them
+        // there (no host packing, no upload)
+        const OpenSrc src{cs->coset_in, 7 * (n + 3), cs->stage, 5 * (n + 3)};
+        int orc = open_dev(pk, w, src, k, st.data(), cs->q_all, cs->ntt_tmp);
+        if (orc != RNG_OK) return orc;
+        std::vector<G1Jac> res(2 * (size_t)k);
+        if (n + 2 > ctx->srs_count ||
+            commit_staged_jac(ctx, cs->ntt_tmp, cs->canon, n + 2, 2 * k, res.data()) != RNG_OK)
+            return RNG_ERR_HIP;
+        pool.parallel_for(2 * k, [&](uint32_t b) { jac_to_affine(res[b], &cbuf[b], &ibuf[b]); });
+    } else {
+        std::vector<std::vector<Fr>> Wz(k), Wzw(k);
+        pool.parallel_for(k, [&](uint32_t p) { rounds_4_5(pk, w, st[p], Wz[p], Wzw[p]); });
+        for (uint32_t p = 0; p < k; ++p) {
+            ps[2 * (size_t)p] = &Wz[p];
+            ps[2 * (size_t)p + 1] = &Wzw[p];
+        }
+        if (commit_cohort(ctx, ps.data(), 2 * k, cbuf.data(), ibuf.get()) != RNG_OK)
+            return RNG_ERR_HIP;
     }
-    if (commit_cohort(ctx, ps.data(), 2 * k, cbuf.data(), ibuf.get()) != RNG_OK)
-        return RNG_ERR_HIP;
     pool.parallel_for(k, [&](uint32_t p) {
         st[p].take_comms(COMM_WZ, 2, &cbuf[2 * (size_t)p], &ibuf[2 * (size_t)p]);
         st[p].serialize(out_proofs + (size_t)p * 157);
@@ -1915,6 +2162,12 @@ static int plonk_preprocess_impl(RngCtxImpl* ctx, const RngCircuitDesc* d,
     HIP_CHECK(hipMemcpy(pk->sig_evals_dev, sig_evals_flat.data(), 5 * n * sizeof(Fr),
                         hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(pk->wpow_dev, wpow.data(), n * sizeof(Fr), hipMemcpyHostToDevice));
+    // coefficient forms for the R4 + R5 stage (18n Fr per key)
+    HIP_CHECK(hipMalloc(&pk->coef_dev, 18 * n * sizeof(Fr)));
+    for (int s = 0; s < 18; ++s)
+        HIP_CHECK(hipMemcpy(pk->coef_dev + (size_t)s * n,
+                            s < 13 ? pk->selq[s].data() : pk->sigp[s - 13].data(),
+                            n * sizeof(Fr), hipMemcpyHostToDevice));
 
     // commitments (two fused batch MSMs)
     {
@@ -2101,10 +2354,32 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wi
     }
     st.zeta = st.tr.challenge();
 
-    // --- R4 + R5: evaluations, linearization, openings (host) ---
-    std::vector<Fr> Wz, Wzw;
-    rounds_4_5(pk, w, st, Wz, Wzw);
-    {
+    // --- R4 + R5: evaluations, linearization, openings (device stage or
+    //     host) ---
+    if (ProverEnv::on(prover_env().open_device, OPEN_DEVICE_DEFAULT_SINGLE) &&
+        n <= OPEN_MAX_N) {
+        // this path holds the blinded polynomials on the host: one packed
+        // upload of the 11 into stage (13 slots of n + 3); C and the two
+        // quotients go to q_buf, free since the inverse coset transform
+        const size_t stride = n + 3;
+        std::vector<Fr> packed(OPEN_PROOF_POLYS * stride, Fr::zero());
+        for (int j = 0; j < OPEN_PROOF_POLYS; ++j) {
+            const std::vector<Fr>& src = j < 5 ? wpoly[j] : j == 5 ? zpoly : quot_chunks[j - 6];
+            memcpy(packed.data() + j * stride, src.data(), src.size() * sizeof(Fr));
+        }
+        HIP_CHECK(hipMemcpyAsync(sc->stage, packed.data(), packed.size() * sizeof(Fr),
+                                 hipMemcpyHostToDevice, RNG_STREAM));
+        const OpenSrc src{sc->stage, 0, sc->stage + 6 * stride, 0};
+        Fr* Wd = sc->q_buf + stride;
+        int orc = open_dev(pk, w, src, 1, &st, sc->q_buf, Wd);
+        if (orc != RNG_OK) return orc;
+        G1Jac res[2];
+        if (commit_staged_jac(ctx, Wd, sc->canon, n + 2, 2, res) != RNG_OK)
+            return RNG_ERR_HIP;
+        for (int b = 0; b < 2; ++b) jac_to_affine(res[b], &cbuf[b], &ibuf[b]);
+    } else {
+        std::vector<Fr> Wz, Wzw;
+        rounds_4_5(pk, w, st, Wz, Wzw);
         const std::vector<Fr>* ps[2] = {&Wz, &Wzw};
         if (commit_dev_batch(ctx, ps, 2, cbuf, ibuf) != RNG_OK) return RNG_ERR_HIP;
     }
@@ -2754,6 +3029,95 @@ int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wi
     HostPool::inst().parallel_for((uint32_t)batch, [&](uint32_t p) {
         perm_product_host(impl, w, (const Fr*)wires + (size_t)5 * p * n, bg[2 * p],
                           bg[2 * p + 1], (Fr*)out_z + (size_t)p * n);
+    });
+    return RNG_OK;
+}
+
+int rng_poly_horner(RngCtx* ctx, const uint64_t* polys, uint64_t len, uint64_t group,
+                    uint64_t batch, int shared, const uint64_t* points, int mode,
+                    uint64_t* out) {
+    if (!gpu_ok()) return RNG_ERR_NO_GPU;
+    if (!ctx || !polys || !points || !out || !open_shape_ok(len, group, batch, mode))
+        return RNG_ERR_BAD_ARG;
+    OpenScratch* os = open_scratch_get();
+    if (!os) return RNG_ERR_HIP;
+    const size_t nseq = (size_t)batch * group;
+    const size_t in_elems = (shared ? (size_t)group : nseq) * len;
+    const size_t out_elems = mode == 0 ? nseq : nseq * (len - 1);
+    Fr* d = nullptr;  // polys | points | out
+    HIP_CHECK(hipMalloc(&d, (in_elems + batch + out_elems) * sizeof(Fr)));
+    Fr *d_pts = d + in_elems, *d_out = d_pts + batch;
+    OpenSeqs q{};
+    q.src = d, q.item_stride = shared ? 0 : group * len, q.poly_stride = len;
+    q.pts = d_pts, q.pt_stride = 1;
+    q.len = (uint32_t)len, q.group = (uint32_t)group;
+    q.out = d_out, q.out_item_stride = group * (len - 1), q.out_poly_stride = len - 1;
+    int rc = RNG_OK;
+    if (hipMemcpyAsync(d, polys, in_elems * sizeof(Fr), hipMemcpyHostToDevice, RNG_STREAM) !=
+            hipSuccess ||
+        hipMemcpyAsync(d_pts, points, batch * sizeof(Fr), hipMemcpyHostToDevice,
+                       RNG_STREAM) != hipSuccess)
+        rc = RNG_ERR_HIP;
+    if (rc == RNG_OK) rc = horner_dev(os, q, (uint32_t)batch, mode, d_out);
+    if (rc == RNG_OK &&
+        (hipMemcpyAsync(out, d_out, out_elems * sizeof(Fr), hipMemcpyDeviceToHost,
+                        RNG_STREAM) != hipSuccess ||
+         hipStreamSynchronize(RNG_STREAM) != hipSuccess))
+        rc = RNG_ERR_HIP;
+    hipFree(d);
+    return rc;
+}
+
+int rng_open_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t* polys,
+                const uint64_t* points, const uint64_t* scalars, int mode, uint64_t* out_w) {
+    if (!gpu_ok()) return RNG_ERR_NO_GPU;
+    if (!ctx || !pk || !polys || !points || !scalars || !out_w || k < 1 ||
+        k > OPEN_MAX_BATCH || mode < 0 || mode > 2)
+        return RNG_ERR_BAD_ARG;
+    const PlonkPkImpl& impl = pk->impl;
+    const uint64_t n = impl.n;
+    const size_t stride = n + 3, item = OPEN_PROOF_POLYS * stride, wlen = 2 * (n + 2);
+    bool dev = mode == 1;
+    if (mode == 0)  // rng_prove_cohort sends k = 1 down the single-proof path
+        dev = ProverEnv::on(prover_env().open_device, k == 1 ? OPEN_DEVICE_DEFAULT_SINGLE
+                                                             : OPEN_DEVICE_DEFAULT_COHORT) &&
+              n <= OPEN_MAX_N;
+    if (dev) {
+        if (n > OPEN_MAX_N) return RNG_ERR_BAD_ARG;
+        Fr* d = nullptr;  // polys | C | W
+        HIP_CHECK(hipMalloc(&d, k * (item + stride + wlen) * sizeof(Fr)));
+        Fr *d_c = d + k * item, *d_w = d_c + k * stride;
+        int rc = RNG_OK;
+        if (hipMemcpyAsync(d, polys, k * item * sizeof(Fr), hipMemcpyHostToDevice,
+                           RNG_STREAM) != hipSuccess)
+            rc = RNG_ERR_HIP;
+        const OpenSrc src{d, item, d + 6 * stride, item};
+        if (rc == RNG_OK)
+            rc = open_combine_dev(impl, src, (uint32_t)k, (const Fr*)points,
+                                  (const Fr*)scalars, d_c, d_w);
+        if (rc == RNG_OK &&
+            (hipMemcpyAsync(out_w, d_w, k * wlen * sizeof(Fr), hipMemcpyDeviceToHost,
+                            RNG_STREAM) != hipSuccess ||
+             hipStreamSynchronize(RNG_STREAM) != hipSuccess))
+            rc = RNG_ERR_HIP;
+        hipFree(d);
+        return rc;
+    }
+    HostPool::inst().parallel_for((uint32_t)k, [&](uint32_t p) {
+        const Fr* base = (const Fr*)polys + p * item;
+        std::vector<Fr> v[OPEN_PROOF_POLYS];
+        const std::vector<Fr>* ps[OPEN_PROOF_POLYS];
+        for (int j = 0; j < OPEN_PROOF_POLYS; ++j) {  // true lengths
+            const size_t len = (j < 5 || j == 10) ? n + 2 : n + 3;
+            v[j].assign(base + j * stride, base + j * stride + len);
+            ps[j] = &v[j];
+        }
+        const Fr* pt = (const Fr*)points + 2 * (size_t)p;
+        std::vector<Fr> Wz, Wzw;
+        open_host(impl, ps, (const Fr*)scalars + (size_t)OPEN_COUNT * p, pt[0], pt[1], Wz, Wzw);
+        Fr* o = (Fr*)out_w + p * wlen;
+        memcpy(o, Wz.data(), (n + 2) * sizeof(Fr));
+        memcpy(o + (n + 2), Wzw.data(), (n + 2) * sizeof(Fr));
     });
     return RNG_OK;
 }

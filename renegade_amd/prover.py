@@ -76,6 +76,11 @@ class ProverLib:
         self.lib.rng_perm_product_pk.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _U64P,
                                                  _U64P, ctypes.c_uint64, ctypes.c_int,
                                                  _U64P]
+        self.lib.rng_poly_horner.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_uint64,
+                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                             _U64P, ctypes.c_int, _U64P]
+        self.lib.rng_open_pk.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                         _U64P, _U64P, _U64P, ctypes.c_int, _U64P]
         self.lib.rng_srs_dev_bases.restype = ctypes.c_void_p
         self.lib.rng_srs_dev_bases.argtypes = [ctypes.c_void_p, _U64P]
 
@@ -219,6 +224,46 @@ class ProverCtx:
                                                  _ptr(beta_gamma), batch, mode,
                                                  _ptr(out)), "rng_perm_product_pk")
         return out.reshape(batch, n, 4)
+
+    HORNER_EVAL, HORNER_DIVIDE = 0, 1
+
+    def poly_horner(self, polys: np.ndarray, points: np.ndarray, length: int,
+                    group: int = 1, batch: int = 1, shared: bool = False,
+                    mode: int = 0):
+        """Batched Horner scan on the GPU.  Montgomery limbs: polys
+        batch*group*length Fr (group*length when shared), points batch Fr.
+        HORNER_EVAL returns the evaluations, (batch, group, 4); HORNER_DIVIDE
+        the quotients by (X - point), (batch, group, length - 1, 4)."""
+        assert polys.dtype == np.uint64 and points.dtype == np.uint64
+        assert polys.size == 4 * length * group * (1 if shared else batch)
+        assert points.size == 4 * batch
+        polys = np.ascontiguousarray(polys).reshape(-1)
+        points = np.ascontiguousarray(points).reshape(-1)
+        per_seq = 1 if mode == self.HORNER_EVAL else length - 1
+        out = np.zeros(4 * batch * group * per_seq, dtype=np.uint64)
+        self._check(self.lib.rng_poly_horner(self.h, _ptr(polys), length, group, batch,
+                                             1 if shared else 0, _ptr(points), mode,
+                                             _ptr(out)), "rng_poly_horner")
+        if mode == self.HORNER_EVAL:
+            return out.reshape(batch, group, 4)
+        return out.reshape(batch, group, length - 1, 4)
+
+    OPEN_AUTO, OPEN_DEVICE, OPEN_HOST = 0, 1, 2
+
+    def open_pk(self, pk, polys: np.ndarray, points: np.ndarray, scalars: np.ndarray,
+                n: int, k: int = 1, mode: int = 0):
+        """The provers' own call for the batched opening against proving key
+        `pk` (domain size n): polys k*11*(n+3) Fr (wires 0..4, z, chunks 0..4,
+        zero-padded), points k*(zeta, zeta*w), scalars k*29 in the order of
+        open_scalars.  mode: OPEN_AUTO / OPEN_DEVICE / OPEN_HOST.  Returns
+        (k, 2, n + 2, 4): W_zeta and W_zeta_w of each proof."""
+        for a, fr in ((polys, 11 * (n + 3) * k), (points, 2 * k), (scalars, 29 * k)):
+            assert a.dtype == np.uint64 and a.size == 4 * fr
+        args = [np.ascontiguousarray(a).reshape(-1) for a in (polys, points, scalars)]
+        out = np.zeros(4 * 2 * (n + 2) * k, dtype=np.uint64)
+        self._check(self.lib.rng_open_pk(self.h, ctypes.c_void_p(pk), k, *map(_ptr, args),
+                                         mode, _ptr(out)), "rng_open_pk")
+        return out.reshape(k, 2, n + 2, 4)
 
     # ---- device-resident helpers (benchmarking) ----
     def dbuf_from(self, host: np.ndarray):
