@@ -14,6 +14,9 @@
 //          to k2 + N2*k1 (natural order out).
 //    Column/row PAIRS make every global access a 64-byte aligned segment
 //    (2 adjacent Fr of 32 B), the HBM sector size — full-bandwidth pattern.
+//    Passes with a DFT length of at most 256 (log2 n 11..17) take 512 / N
+//    columns (rows) per 256-thread block instead, so that every lane has a
+//    butterfly: k_ntt_col_fill / k_ntt_row_fill at the end of this file.
 //  - LDS element indices are XOR-swizzled so power-of-two-strided butterfly
 //    accesses spread across the 64 LDS banks.
 // All twiddles are precomputed per (n, direction) into HBM once per plan.
@@ -159,6 +162,94 @@ __global__ __launch_bounds__(512) void k_ntt_row(const Fr* in, Fr* out, const Fr
     // element [c][k1] -> global position k2 + N2*k1, k2 = PW*wg + c
     for (uint32_t q = threadIdx.x; q < PW * N1; q += blockDim.x) {
         uint32_t k1 = q / PW, c = q % PW;
+        Fr v = lds[lds_slot(c * N1 + k1)];
+        if (do_scale) v = v.mul(scale);
+        obase[(PW * wg + c) + (uint64_t)N2 * k1] = v;
+    }
+}
+
+// ---- filled blocks: the same two passes for DFT lengths N <= 256 ----
+// The kernels above run PW * N / 2 butterflies per stage in a 512-thread
+// block, so with PW = 2 and N = 64 one wave of eight works and seven wait at
+// the barrier.  Here a block takes PW = 512 / N columns (rows): 256 threads,
+// 512 elements (16 KiB LDS), every thread one butterfly per stage and two
+// elements of the load and of the store.  Eight blocks fit a CU (32 waves,
+// 128 KiB LDS) and every wave works.  Global accesses are PW * 32-byte
+// segments.  Index maps, swizzle and arithmetic are those of k_ntt_col /
+// k_ntt_row, so results are the same bit for bit.
+constexpr uint32_t NTT_FILL_THREADS = 256;
+constexpr uint32_t NTT_FILL_ELEMS = 2 * NTT_FILL_THREADS;
+
+// All stages of the PW length-N DFTs that lie back to back in lds.  Thread t
+// owns butterfly t & (N/2 - 1) of DFT t / (N/2); as N/2 is a multiple of
+// every half, the element index needs neither of the two.
+__device__ __forceinline__ void ntt_fill_stages(Fr* lds, const Fr* wst, uint32_t logN) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t s = 1; s <= logN; ++s) {
+        uint32_t half = 1u << (s - 1);
+        uint32_t k = t & (half - 1);
+        uint32_t i0 = ((t >> (s - 1)) << s) + k;
+        uint32_t i1 = i0 + half;
+        Fr tw = wst[k << (logN - s)];
+        Fr u = lds[lds_slot(i0)];
+        Fr v = lds[lds_slot(i1)].mul(tw);
+        lds[lds_slot(i0)] = u.add(v);
+        lds[lds_slot(i1)] = u.sub(v);
+        __syncthreads();
+    }
+}
+
+// grid.x = N1/PW * batch, PW = 1 << logPW = NTT_FILL_ELEMS / N2 <= N1.
+__global__ __launch_bounds__(NTT_FILL_THREADS, 8) void k_ntt_col_fill(
+    Fr* data, const Fr* wst2, const Fr* ta, const Fr* tb, uint32_t N1, uint32_t N2,
+    uint32_t logN2, uint32_t split_log, uint32_t logPW) {
+    extern __shared__ Fr lds[];
+    const uint32_t PW = 1u << logPW;
+    uint32_t wg = blockIdx.x % (N1 >> logPW);
+    Fr* base = data + (uint64_t)(blockIdx.x / (N1 >> logPW)) * N1 * N2;
+    uint32_t split_mask = (1u << split_log) - 1;
+
+#pragma unroll
+    for (uint32_t q = threadIdx.x; q < NTT_FILL_ELEMS; q += NTT_FILL_THREADS) {
+        uint32_t m = q >> logPW, c = q & (PW - 1);
+        Fr v = base[(PW * wg + c) + (uint64_t)N1 * m];
+        lds[lds_slot(c * N2 + brev_n(m, logN2))] = v;
+    }
+    __syncthreads();
+    ntt_fill_stages(lds, wst2, logN2);
+#pragma unroll
+    for (uint32_t q = threadIdx.x; q < NTT_FILL_ELEMS; q += NTT_FILL_THREADS) {
+        uint32_t k2 = q >> logPW, c = q & (PW - 1);
+        uint32_t j1 = PW * wg + c;
+        Fr tw = ta[(uint64_t)j1 * (k2 >> split_log)].mul(tb[(uint64_t)j1 * (k2 & split_mask)]);
+        base[j1 + (uint64_t)N1 * k2] = lds[lds_slot(c * N2 + k2)].mul(tw);
+    }
+}
+
+// grid.x = N2/PW * batch, PW = 1 << logPW = NTT_FILL_ELEMS / N1 <= N2.
+__global__ __launch_bounds__(NTT_FILL_THREADS, 8) void k_ntt_row_fill(
+    const Fr* in, Fr* out, const Fr* wst1, uint32_t N1, uint32_t N2, uint32_t logN1,
+    uint32_t logPW, Fr scale, int do_scale) {
+    extern __shared__ Fr lds[];
+    const uint32_t PW = 1u << logPW;
+    uint32_t wg = blockIdx.x % (N2 >> logPW);
+    uint64_t boff = (uint64_t)(blockIdx.x / (N2 >> logPW)) * N1 * N2;
+    const Fr* ibase = in + boff;
+    Fr* obase = out + boff;
+
+#pragma unroll
+    for (uint32_t q = threadIdx.x; q < NTT_FILL_ELEMS; q += NTT_FILL_THREADS) {
+        uint32_t c = q >> logN1;
+        uint32_t j1 = q & (N1 - 1);
+        Fr v = ibase[(uint64_t)(PW * wg) * N1 + q];
+        lds[lds_slot(c * N1 + brev_n(j1, logN1))] = v;
+    }
+    __syncthreads();
+    ntt_fill_stages(lds, wst1, logN1);
+    // element [c][k1] -> global position k2 + N2*k1, k2 = PW*wg + c
+#pragma unroll
+    for (uint32_t q = threadIdx.x; q < NTT_FILL_ELEMS; q += NTT_FILL_THREADS) {
+        uint32_t k1 = q >> logPW, c = q & (PW - 1);
         Fr v = lds[lds_slot(c * N1 + k1)];
         if (do_scale) v = v.mul(scale);
         obase[(PW * wg + c) + (uint64_t)N2 * k1] = v;

@@ -298,6 +298,9 @@ static constexpr uint32_t NTT_SMALL_MAX = 1024;
 // 128 KiB dynamic request is granted by the plain launch below
 // (tests/test_ntt_tiers.py compares 2^23 and 2^24 in full).
 static constexpr uint64_t NTT_MAX_N = 1ull << 24;
+// filled 256-thread blocks for passes with N <= 256 (log2 n 11..17), decided
+// by the headline A/B of profiles/ntt_filled_blocks_ab.json
+static constexpr bool NTT_FILL_DEFAULT = true;
 
 // public-API argument contract (include/rng_prover.h), checked before any
 // allocation, copy or plan construction
@@ -387,13 +390,28 @@ static int ntt_dev_run(RngCtxImpl* ctx, Fr* data, Fr* out, uint32_t n, uint64_t 
         const char* e = getenv("RNG_NTT_PAIR_LDS");  // A/B knob, bytes
         return e ? (uint32_t)atoi(e) : 65536u;
     }();
+    // filled blocks for passes with N <= 256 (ntt_kernels.hip): PW = 512 / N
+    // columns (rows) per 256-thread block.  RNG_NTT_FILL=0 keeps the 512-thread
+    // pair kernels at every size, for A/B runs
+    static const bool fill = [] {
+        const char* e = getenv("RNG_NTT_FILL");
+        return e ? atoi(e) != 0 : NTT_FILL_DEFAULT;
+    }();
+    const uint32_t fpw1 = NTT_FILL_ELEMS / p->N2, fpw2 = NTT_FILL_ELEMS / p->N1;
+    const bool fill1 = fill && fpw1 >= 2 && fpw1 <= p->N1;
+    const bool fill2 = fill && fpw2 >= 2 && fpw2 <= p->N2;
     const uint32_t pw1 = (2u * p->N2 * sizeof(Fr) <= pw_lds_cap) ? 2 : 1;
     const uint32_t pw2 = (2u * p->N1 * sizeof(Fr) <= pw_lds_cap) ? 2 : 1;
     uint32_t lds1 = pw1 * p->N2 * sizeof(Fr);
     uint32_t lds2 = pw2 * p->N1 * sizeof(Fr);
     EvtTimer et;
     et.mark(stream);
-    if (pw1 == 2)
+    if (fill1)
+        hipLaunchKernelGGL(k_ntt_col_fill, dim3((uint32_t)(p->N1 / fpw1 * batch)),
+                           dim3(NTT_FILL_THREADS), NTT_FILL_ELEMS * sizeof(Fr), stream, data,
+                           wst2, ta, tb, p->N1, p->N2, p->logN2, p->split_log,
+                           (uint32_t)__builtin_ctz(fpw1));
+    else if (pw1 == 2)
         hipLaunchKernelGGL(k_ntt_col<2>, dim3((uint32_t)(p->N1 / 2 * batch)), dim3(512),
                            lds1, stream, data, wst2, ta, tb, p->N1, p->N2, p->logN2,
                            p->split_log);
@@ -403,7 +421,12 @@ static int ntt_dev_run(RngCtxImpl* ctx, Fr* data, Fr* out, uint32_t n, uint64_t 
                            p->split_log);
     HIP_CHECK(hipGetLastError());
     et.mark(stream);
-    if (pw2 == 2)
+    if (fill2)
+        hipLaunchKernelGGL(k_ntt_row_fill, dim3((uint32_t)(p->N2 / fpw2 * batch)),
+                           dim3(NTT_FILL_THREADS), NTT_FILL_ELEMS * sizeof(Fr), stream, data,
+                           out, wst1, p->N1, p->N2, p->logN1, (uint32_t)__builtin_ctz(fpw2),
+                           p->ninv, inverse ? 1 : 0);
+    else if (pw2 == 2)
         hipLaunchKernelGGL(k_ntt_row<2>, dim3((uint32_t)(p->N2 / 2 * batch)), dim3(512),
                            lds2, stream, data, out, wst1, p->N1, p->N2, p->logN1,
                            p->ninv, inverse ? 1 : 0);
