@@ -223,23 +223,24 @@ int rng_prove(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wires,
  * wires = k consecutive 5n-scalar wire blocks, public_inputs = k consecutive
  * statement blocks, seeds = k blinder seeds; out_proofs = k consecutive
  * 157-u64 proofs; out_link_hints (optional) = k consecutive hint buffers.
- * Proof p is bit-identical to rng_prove with seeds[p].  1 <= k <= 128. */
+ * Proof p is bit-identical to rng_prove with seeds[p], which is this call
+ * with k = 1.  1 <= k <= 128. */
 int rng_prove_cohort(RngCtx* ctx, const RngProvingKey* pk, uint64_t k,
                      const uint64_t* wires, const uint64_t* public_inputs,
                      const uint64_t* seeds, uint64_t* out_proofs,
                      uint64_t* out_link_hints);
 
 /* Test hook in the style of rng_msm_srs_batch: the SAME internal call the
- * provers' round 2 makes, against the key's own sigma/omega tables (wires,
+ * prover's round 2 makes, against the key's own sigma/omega tables (wires,
  * beta_gamma and out_z as in rng_perm_product, n = the key's domain size).
- * mode 0 = what the prover would pick (RNG_Z_DEVICE, else the per-path
- * default; batch 1 is the single-proof path), 1 = device, 2 = host loop. */
+ * mode 0 = what the prover would pick (RNG_Z_DEVICE, else the default, the
+ * same for every batch), 1 = device, 2 = host loop. */
 int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wires,
                         const uint64_t* beta_gamma, uint64_t batch, int mode,
                         uint64_t* out_z);
 
 /* Test hook in the style of rng_perm_product_pk: the SAME internal call the
- * provers' rounds 4 and 5 make once the 29 scalars of the batched opening
+ * prover's rounds 4 and 5 make once the 29 scalars of the batched opening
  * are known, against the key's own selector and sigma coefficients (n = the
  * key's domain size).  Per proof p:
  *   C_p      = sum_t scalars[p][t] * P_t   (13 selectors, sigma_0..3, sigma_4,
@@ -249,8 +250,8 @@ int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wi
  * coefficients), z (n+3), chunks 0..3 (n+3), chunk 4 (n+2), each zero-padded
  * to n+3; points = k x 2; scalars = k x 29; out_w = k x 2 x (n+2): W_zeta
  * then W_zeta_w of each proof.  1 <= k <= 128.
- * mode 0 = what the prover would pick (RNG_OPEN_DEVICE, else the per-path
- * default; k = 1 is the single-proof path), 1 = device, 2 = host loops. */
+ * mode 0 = what the prover would pick (RNG_OPEN_DEVICE, else the default,
+ * the same for every k), 1 = device, 2 = host loops. */
 int rng_open_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t* polys,
                 const uint64_t* points, const uint64_t* scalars, int mode,
                 uint64_t* out_w);

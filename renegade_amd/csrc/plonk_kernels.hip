@@ -4,9 +4,9 @@
 // (the dominant non-NTT/MSM column work of the prover):
 //   num(t) = gate(t) + alpha [ z f - z_shift g ] + alpha^2 (z-1) L1
 //   quot(t) = num(t) * zh_inv[t % 8]
-// One thread per coset point; all operands are coset-evaluation arrays laid
-// out contiguously (sel: 13*m, sig: 5*m, w: 5*m, z/pi/l1: m, xpow: m = the
-// coset points g*w_m^t for the beta*k_j*X term).
+// One thread per coset point of one proof; all operands are coset-evaluation
+// arrays laid out contiguously (sel: 13*m, sig: 5*m, l1: m, xpow: m = the
+// coset points g*w_m^t for the beta*k_j*X term; per proof w: 5*m, z/pi: m).
 #include <hip/hip_runtime.h>
 #include "gpu_field.hpp"
 
@@ -18,45 +18,11 @@ struct QuotChal {  // challenge pack (kernel arg)
     Fr zh_inv[8];
 };
 
-__global__ __launch_bounds__(256) void k_quotient(
-    const Fr* sel, const Fr* sig, const Fr* w, const Fr* z, const Fr* pi,
-    const Fr* l1, const Fr* xpow, Fr* out, uint32_t m, QuotChal ch) {
-    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= m) return;
-    auto p5 = [](const Fr& v) {
-        Fr v2 = v.sqr();
-        return v2.sqr().mul(v);
-    };
-    Fr w0 = w[t], w1 = w[m + t], w2 = w[2 * m + t], w3 = w[3 * m + t],
-       w4 = w[4 * m + t];
-    // gate equation: selector order = plonk_circuit.hpp enum Sel
-    Fr gate = sel[11 * m + t].add(pi[t]);
-    gate = gate.add(sel[0 * m + t].mul(w0)).add(sel[1 * m + t].mul(w1));
-    gate = gate.add(sel[2 * m + t].mul(w2)).add(sel[3 * m + t].mul(w3));
-    gate = gate.add(sel[4 * m + t].mul(w0.mul(w1))).add(sel[5 * m + t].mul(w2.mul(w3)));
-    gate = gate.add(sel[6 * m + t].mul(p5(w0))).add(sel[7 * m + t].mul(p5(w1)));
-    gate = gate.add(sel[8 * m + t].mul(p5(w2))).add(sel[9 * m + t].mul(p5(w3)));
-    gate = gate.add(sel[12 * m + t].mul(w0.mul(w1).mul(w2).mul(w3).mul(w4)));
-    gate = gate.sub(sel[10 * m + t].mul(w4));
-    // permutation
-    Fr x = xpow[t];
-    Fr f = Fr::one(), g = Fr::one();
-    const Fr* ws[5] = {&w0, &w1, &w2, &w3, &w4};
-    for (int j = 0; j < 5; ++j) {
-        f = f.mul(ws[j]->add(ch.beta.mul(ch.k[j]).mul(x)).add(ch.gamma));
-        g = g.mul(ws[j]->add(ch.beta.mul(sig[j * m + t])).add(ch.gamma));
-    }
-    Fr zshift = z[(t + 8) % m];
-    Fr perm = ch.alpha.mul(z[t].mul(f).sub(zshift.mul(g)));
-    Fr l1term = ch.alpha2.mul(z[t].sub(Fr::one())).mul(l1[t]);
-    out[t] = gate.add(perm).add(l1term).mul(ch.zh_inv[t & 7]);
-}
-
 // cohort-batched quotient: K proofs in one launch (K*m threads) — a single
 // proof's m=8n grid is only ~0.5 waves/SIMD at n=4096, pure latency; the
-// cohort profile showed 483 small k_quotient launches at 14% of GPU time.
+// cohort profile showed 483 small per-proof launches at 14% of GPU time.
 // Wire/z/PI cosets are laid out per proof at stride 7m (slots 0-4 wires,
-// 5 z, 6 PI — plonk_prove_cohort_impl); challenges per proof from HBM.
+// 5 z, 6 PI — plonk_prove_impl); challenges per proof from HBM.
 __global__ __launch_bounds__(256) void k_quotient_batch(
     const Fr* sel, const Fr* sig, const Fr* coset_all, const Fr* l1,
     const Fr* xpow, Fr* out_all, uint32_t m, uint32_t K, const QuotChal* chs) {
@@ -75,6 +41,7 @@ __global__ __launch_bounds__(256) void k_quotient_batch(
     };
     Fr w0 = w[t], w1 = w[m + t], w2 = w[2 * m + t], w3 = w[3 * m + t],
        w4 = w[4 * m + t];
+    // gate equation: selector order = plonk_circuit.hpp enum Sel
     Fr gate = sel[11 * m + t].add(pi[t]);
     gate = gate.add(sel[0 * m + t].mul(w0)).add(sel[1 * m + t].mul(w1));
     gate = gate.add(sel[2 * m + t].mul(w2)).add(sel[3 * m + t].mul(w3));
@@ -83,6 +50,7 @@ __global__ __launch_bounds__(256) void k_quotient_batch(
     gate = gate.add(sel[8 * m + t].mul(p5(w2))).add(sel[9 * m + t].mul(p5(w3)));
     gate = gate.add(sel[12 * m + t].mul(w0.mul(w1).mul(w2).mul(w3).mul(w4)));
     gate = gate.sub(sel[10 * m + t].mul(w4));
+    // permutation
     Fr x = xpow[t];
     Fr f = Fr::one(), g = Fr::one();
     const Fr* ws[5] = {&w0, &w1, &w2, &w3, &w4};
@@ -145,7 +113,7 @@ __global__ __launch_bounds__(256) void k_blind_wires_batch(
 
 // cohort R2: blind the k grand-product polynomials on device; same double
 // write (commit staging at stride n+3, coset slot p*7+5).  Blinder order
-// mirrors plonk_prove_impl: draws (b2,b3,b4) apply as zp[0]-=b4, zp[1]-=b3,
+// mirrors the oracle prover: draws (b2,b3,b4) apply as zp[0]-=b4, zp[1]-=b3,
 // zp[2]-=b2, zp[n]+=b4, zp[n+1]+=b3, zp[n+2]+=b2.
 __global__ __launch_bounds__(256) void k_blind_z_batch(
     const Fr* coeffs, const Fr* blinders /* 3 per proof: b2,b3,b4 */, Fr* out,

@@ -1,8 +1,9 @@
 // PRODUCT PATH — the host half of the five PlonK rounds, written once.
 //
-// rng_prove (plonk_prove_impl), rng_prove_cohort (plonk_prove_cohort_impl)
-// and rng_verify all go through this file for everything that is not device
-// choreography: the per-proof state, the blinder order, rounds 4 and 5, the
+// The prover (plonk_prove_impl: k >= 1 proofs in lockstep, behind rng_prove
+// with k = 1 and rng_prove_cohort) and rng_verify go through this file for
+// everything that is not device choreography: the per-proof state, the
+// blinder order, rounds 4 and 5, the
 // linearization scalars, proof and link-hint serialization and the 9-word
 // affine record.  Host-only: no HIP runtime call, no device pointer.
 #pragma once

@@ -468,8 +468,8 @@ static const MsmEnv& msm_env() {
 }
 
 // The prover's own switches, read once per process.  z_device, r1_lagrange
-// and open_device: -1 = unset (the per-path *_DEFAULT_* constants decide), 0 =
-// off, 1 = on in both provers.
+// and open_device: -1 = unset (Z_DEVICE_DEFAULT, R1_LAGRANGE_MIN_K and
+// OPEN_DEVICE_DEFAULT decide), 0 = off, 1 = on, for every k.
 struct ProverEnv {
     int z_device;      // RNG_Z_DEVICE: R2 grand product on the device
     int r1_lagrange;   // RNG_R1_LAGRANGE: R1 commits in the Lagrange basis
@@ -968,7 +968,7 @@ static int msm_srs_run(RngCtxImpl* ctx, const uint64_t* d_canon, uint64_t m, uin
 // ---- Lagrange-basis commitments of evaluation vectors ----
 
 // internal status: this domain has no Lagrange bases (a base at infinity,
-// n + 2 > srs_count, no table slot or memory); provers fall back to the
+// n + 2 > srs_count, no table slot or memory); the prover falls back to the
 // coefficient path, the test hook reports RNG_ERR_BAD_ARG
 constexpr int MSM_LAGRANGE_UNUSABLE = -100;
 
@@ -1090,7 +1090,7 @@ static const G1Aff* msm_lagrange_table(RngCtxImpl* ctx, uint64_t n, uint32_t c) 
 // remains, so they take the smallest table-backed window (c = 8 beat 10 and
 // 13 at the settlement cohort shape: DESIGN §4.1).  A dense witness (more
 // than half of the scalars non-zero; the validity circuits are at 86-96 %)
-// gains nothing here: 0 tells the provers to commit the coefficients as
+// gains nothing here: 0 tells the prover to commit the coefficients as
 // before, so such a domain never builds bases or tables.  The 1/2 threshold
 // is reasoned, not tuned: the circuits sit at 19 % and at 86 % and above.
 // The test hook commits dense input at MSM_LAGRANGE_DENSE_C whatever B is,
@@ -1143,11 +1143,11 @@ static int msm_lagrange_run(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon
 }
 
 // RNG_R1_LAGRANGE (ProverEnv::r1_lagrange): 0 = round 1 commits the blinded
-// coefficients, 1 = commits the evaluations against the Lagrange bases in
-// both provers, unset = the per-path defaults below (the A/B behind them:
-// DESIGN §4.1, profiles/lagrange_commit_ab.json).
-constexpr bool R1_LAGRANGE_DEFAULT_SINGLE = false;
-constexpr bool R1_LAGRANGE_DEFAULT_COHORT = true;
+// coefficients, 1 = commits the evaluations against the Lagrange bases, for
+// every k.  Unset: on from this cohort size up.  One proof (B = 5) measured
+// no gain and its first prove pays the bases build (DESIGN §4.1, table row
+// `--jobs 1`; profiles/lagrange_commit_ab.json); cohorts gain.
+constexpr uint32_t R1_LAGRANGE_MIN_K = 2;
 
 // ---------------- TurboPlonk prover (GPU) ----------------
 
@@ -1181,33 +1181,16 @@ static int coset_fwd_dev(RngCtxImpl* ctx, Fr* in, Fr* out, uint32_t m) {
     return ntt_dev_run(ctx, in, out, m, 1, false, RNG_STREAM);
 }
 
-// inverse coset NTT of `in` (m evals), result into `out`
-static int coset_inv_dev(RngCtxImpl* ctx, Fr* in, Fr* out, uint32_t m) {
-    NttPlan* p = get_plan(ctx, m, 1);
-    if (!p) return RNG_ERR_HIP;
-    if (ensure_coset_tables(ctx, p) != RNG_OK) return RNG_ERR_HIP;
-    int rc = ntt_dev_run(ctx, in, out, m, 1, true, RNG_STREAM);
-    if (rc != RNG_OK) return rc;
-    uint32_t blocks = (m + 255) / 256;
-    hipLaunchKernelGGL(k_mul_pointwise, dim3(blocks), dim3(256), 0, RNG_STREAM, out,
-                       p->gpow_inv, m);
-    HIP_CHECK(hipGetLastError());
-    return RNG_OK;
-}
-
-struct ProveScratch {  // per-context device scratch for proving at size n
-    uint64_t n = 0, m = 0;
-    Fr* w_coset = nullptr;   // 5*m
-    Fr* z_coset = nullptr;   // m
-    Fr* pi_coset = nullptr;  // m
-    Fr* q_buf = nullptr;     // m
-    Fr* tmp = nullptr;       // m
-    Fr* stage = nullptr;     // n+3 coefficient staging
-    uint64_t* canon = nullptr;  // 4*(n+3) canonical scalars for commits
+// per-thread device scratch of preprocessing and link proofs at size n (the
+// prover has its own, CohortScratch)
+struct ProveScratch {
+    static constexpr uint32_t SLOTS = 13;  // one fused commit: the 13 selectors
+    uint64_t n = 0;
+    Fr* tmp = nullptr;       // 8n: padded input of one coset transform
+    Fr* stage = nullptr;     // SLOTS x (n+3) coefficient staging
+    uint64_t* canon = nullptr;  // SLOTS x 4*(n+3) canonical scalars for commits
     ~ProveScratch() {
-        for (void* b : {(void*)w_coset, (void*)z_coset, (void*)pi_coset, (void*)q_buf,
-                        (void*)tmp, (void*)stage, (void*)canon})
-            hip_free_guarded(b);
+        for (void* b : {(void*)tmp, (void*)stage, (void*)canon}) hip_free_guarded(b);
     }
 };
 
@@ -1229,29 +1212,22 @@ struct PlonkPkImpl : PlonkPkHost {  // host half: plonk_rounds.hpp
 static thread_local std::unique_ptr<ProveScratch> tls_prove_scratch;
 
 static int prove_scratch_ensure(uint64_t n) {
-    uint64_t m = 8 * n;
     if (tls_prove_scratch && tls_prove_scratch->n >= n) return RNG_OK;
     tls_prove_scratch = std::make_unique<ProveScratch>();
     ProveScratch* s = tls_prove_scratch.get();
-    HIP_CHECK(hipMalloc(&s->w_coset, 5 * m * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->z_coset, m * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->pi_coset, m * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->q_buf, m * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->tmp, m * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->stage, 13 * (n + 3) * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->canon, 13 * 4 * (n + 3) * 8));
+    HIP_CHECK(hipMalloc(&s->tmp, 8 * n * sizeof(Fr)));
+    HIP_CHECK(hipMalloc(&s->stage, ProveScratch::SLOTS * (n + 3) * sizeof(Fr)));
+    HIP_CHECK(hipMalloc(&s->canon, ProveScratch::SLOTS * 4 * (n + 3) * 8));
     s->n = n;
-    s->m = m;
     return RNG_OK;
 }
 
 // ---------------- R2: permutation grand product ----------------
 
 // RNG_Z_DEVICE (ProverEnv::z_device): 0 = host loops, 1 = device stage
-// (perm_kernels.hip) in both provers.  Unset: per-path defaults below, set
-// by the A/B measurement in DESIGN.md §4.5.
-constexpr bool Z_DEVICE_DEFAULT_SINGLE = true;
-constexpr bool Z_DEVICE_DEFAULT_COHORT = true;
+// (perm_kernels.hip), for every k.  Unset: the default below, set by the
+// A/B measurement in DESIGN.md §4.5.
+constexpr bool Z_DEVICE_DEFAULT = true;
 
 // host loop: n evaluations of one proof's z into ze
 static void perm_product_host(const PlonkPkImpl& pk, const Fr& w, const Fr* wires,
@@ -1369,7 +1345,7 @@ static int perm_product_dev(const Fr* wires, const Fr* sigma, const Fr* wpow,
 
 // tail of a KZG commit: B polys of m Montgomery coefficients staged on the
 // device -> canonical scalars -> ONE fused MSM over the SRS bases.  The
-// callers turn the Jacobian results affine in a loop of their own.
+// callers turn the Jacobian results affine with jacs_to_affine.
 static int commit_staged_jac(RngCtxImpl* ctx, const Fr* stage, uint64_t* canon, uint64_t m,
                              uint32_t B, G1Jac* res) {
     uint32_t blocks = (uint32_t)((B * m + 255) / 256);
@@ -1380,25 +1356,65 @@ static int commit_staged_jac(RngCtxImpl* ctx, const Fr* stage, uint64_t* canon, 
     return msm_srs_run(ctx, canon, m, B, res);
 }
 
+// B independent Jacobian results -> affine.  On the pool only from B = 8 up:
+// the pool admits one job at a time and every job wakes all its workers, so
+// the five-element jobs of concurrent single proofs would queue on each other.
+static void jacs_to_affine(const G1Jac* res, uint32_t B, G1Aff* out, bool* out_inf) {
+    auto one = [&](uint32_t b) { jac_to_affine(res[b], &out[b], &out_inf[b]); };
+    if (B >= 8)
+        HostPool::inst().parallel_for(B, one);
+    else
+        for (uint32_t b = 0; b < B; ++b) one(b);
+}
+
+// commit B polynomials ALREADY staged on the device in `stage` (B consecutive
+// m-coefficient blocks, Montgomery form; `canon` holds 4 u64 per coefficient)
+static int commit_staged(RngCtxImpl* ctx, const Fr* stage, uint64_t* canon, uint64_t m,
+                         uint32_t B, G1Aff* out, bool* out_inf) {
+    if (m > ctx->srs_count) return RNG_ERR_BAD_ARG;
+    std::vector<G1Jac> res(B);
+    int rc = commit_staged_jac(ctx, stage, canon, m, B, res.data());
+    if (rc != RNG_OK) return rc;
+    jacs_to_affine(res.data(), B, out, out_inf);
+    return RNG_OK;
+}
+
 // commit to B host coefficient vectors via ONE fused GPU MSM over the SRS
-// bases (shorter polys zero-padded; zero scalars cost nothing)
-static int commit_dev_batch(RngCtxImpl* ctx, const std::vector<Fr>* const* polys,
-                            uint32_t B, G1Aff* out, bool* out_inf) {
-    ProveScratch* s = tls_prove_scratch.get();
+// bases (shorter polys zero-padded to the longest; zero scalars cost
+// nothing).  `stage` holds stage_elems coefficients, `canon` 4 u64 for each.
+static int commit_host_polys(RngCtxImpl* ctx, const std::vector<Fr>* const* polys,
+                             uint32_t B, Fr* stage, uint64_t* canon, uint64_t stage_elems,
+                             G1Aff* out, bool* out_inf) {
     uint64_t m = 0;
     for (uint32_t b = 0; b < B; ++b)
         if (polys[b]->size() > m) m = polys[b]->size();
-    if (m > ctx->srs_count || B > 13) return RNG_ERR_BAD_ARG;
-    HIP_CHECK(hipMemsetAsync(s->stage, 0, B * m * sizeof(Fr), RNG_STREAM));
-    for (uint32_t b = 0; b < B; ++b)
-        HIP_CHECK(hipMemcpyAsync(s->stage + b * m, polys[b]->data(),
-                                 polys[b]->size() * sizeof(Fr), hipMemcpyHostToDevice,
-                                 RNG_STREAM));
-    G1Jac res[13];
-    int rc = commit_staged_jac(ctx, s->stage, s->canon, m, B, res);
-    if (rc != RNG_OK) return rc;
-    for (uint32_t b = 0; b < B; ++b) jac_to_affine(res[b], &out[b], &out_inf[b]);
-    return RNG_OK;
+    if (m > ctx->srs_count || B * m > stage_elems) return RNG_ERR_BAD_ARG;
+    // pack on the host and ship ONE H2D copy: B small async copies of
+    // pageable memory each pay a staging round trip.  Plain local (NOT
+    // thread_local): pool workers reference it from their own threads.
+    std::vector<Fr> packed(B * m);
+    auto pack = [&](uint32_t b) {
+        memcpy(packed.data() + (size_t)b * m, polys[b]->data(),
+               polys[b]->size() * sizeof(Fr));
+        memset(packed.data() + (size_t)b * m + polys[b]->size(), 0,
+               (m - polys[b]->size()) * sizeof(Fr));
+    };
+    if (B >= 8)
+        HostPool::inst().parallel_for(B, pack);
+    else
+        for (uint32_t b = 0; b < B; ++b) pack(b);
+    HIP_CHECK(hipMemcpyAsync(stage, packed.data(), B * m * sizeof(Fr), hipMemcpyHostToDevice,
+                             RNG_STREAM));
+    return commit_staged(ctx, stage, canon, m, B, out, out_inf);
+}
+
+// the same out of ProveScratch (preprocessing, link proofs): B <= SLOTS
+// polynomials of at most n + 3 coefficients
+static int commit_dev_batch(RngCtxImpl* ctx, const std::vector<Fr>* const* polys,
+                            uint32_t B, G1Aff* out, bool* out_inf) {
+    ProveScratch* s = tls_prove_scratch.get();
+    return commit_host_polys(ctx, polys, B, s->stage, s->canon,
+                             ProveScratch::SLOTS * (s->n + 3), out, out_inf);
 }
 
 static int commit_dev(RngCtxImpl* ctx, const std::vector<Fr>& coeffs, G1Aff* out,
@@ -1410,11 +1426,10 @@ static int commit_dev(RngCtxImpl* ctx, const std::vector<Fr>& coeffs, G1Aff* out
 // ---------------- R4 + R5: evaluations, linearization, openings ----------------
 
 // RNG_OPEN_DEVICE (ProverEnv::open_device): 0 = the host rounds
-// (rounds_4_5), 1 = the device stage (open_kernels.hip) in both provers.
-// Unset: per-path defaults below, set by the A/B measurement in DESIGN.md
-// §4.5 (profiles/open_device_ab.json).
-constexpr bool OPEN_DEVICE_DEFAULT_SINGLE = true;
-constexpr bool OPEN_DEVICE_DEFAULT_COHORT = true;
+// (rounds_4_5), 1 = the device stage (open_kernels.hip), for every k.
+// Unset: the default below, set by the A/B measurement in DESIGN.md §4.5
+// (profiles/open_device_ab.json).
+constexpr bool OPEN_DEVICE_DEFAULT = true;
 static_assert(OPEN_TERMS == OPEN_COUNT, "k_open_lincomb follows open_scalars");
 
 // the ten evaluations of every proof of a full cohort, and any one call
@@ -1424,7 +1439,7 @@ static_assert(OPEN_MAX_EVALS >= OPEN_MAX_SEQ, "one call's results fit");
 struct OpenScratch {  // per-thread small buffers of the device stage (~2.7 MiB)
     Fr* dev = nullptr;      // one allocation, carved below
     Fr* tile_io = nullptr;  // OPEN_MAX_SEQ * OPEN_MAX_TILES tile totals / carries
-    Fr* pts = nullptr;      // OPEN_MAX_SEQ points (the provers: k x (zeta, zeta*w))
+    Fr* pts = nullptr;      // OPEN_MAX_SEQ points (the prover: k x (zeta, zeta*w))
     Fr* evals = nullptr;    // OPEN_MAX_EVALS reduce-mode results
     Fr* scal = nullptr;     // OPEN_MAX_BATCH x 29 scalars
     std::vector<Fr> h_up, h_evals;  // host staging (outlives the async copies)
@@ -1602,23 +1617,25 @@ static int open_dev(const PlonkPkImpl& pk, const Fr& w, const OpenSrc& src, uint
     return open_combine_dev(pk, src, k, points.data(), scalars.data(), C, W);
 }
 
-// ---------------- cohort proving ----------------
+// ---------------- the prover: cohorts of k >= 1 proofs ----------------
 // The reference proves many jobs concurrently from a rayon pool
 // (native_proof_manager.rs:143-148,193-198).  Per-proof GPU runs at n=4096
 // are aggregation-latency chains (r01 profile: window_combine 30% +
-// seg_merge 22% of proof-workload GPU time), so the cohort prover advances
-// k proofs in LOCKSTEP — R1 for all, R2 for all, … — and fuses each round's
+// seg_merge 22% of proof-workload GPU time), so the prover advances k
+// proofs in LOCKSTEP — R1 for all, R2 for all, … — and fuses each round's
 // commitments into ONE msm_dev_run (key group g = poly*W + window already
 // supports a batch dimension).  Transcripts and blinders stay per-proof (one
-// ProofState each, which consumes only its own commitments) and the host
-// rounds are plonk_prove_impl's own (plonk_rounds.hpp), so cohort proofs are
-// bit-identical to rng_prove with the same seed.  Host-side phases (grand
-// product, evaluations, linearization) run on a persistent worker pool
-// (HostPool, defined before msm_dev_run so its window fold can use it).
+// ProofState each, which consumes only its own commitments, through the
+// host rounds of plonk_rounds.hpp), so a proof's bytes depend on its seed
+// and inputs alone, not on k or its place in the cohort; rng_prove is the
+// cohort of one.  Host-side phases (grand product, evaluations,
+// linearization) run on a persistent worker pool (HostPool, defined before
+// msm_dev_run so its window fold can use it).
 
-struct CohortScratch {  // per-thread device scratch for cohort proving
-    uint64_t n = 0, k = 0;
+struct CohortScratch {  // per-thread device scratch of the prover
+    uint64_t elems = 0, k = 0;  // capacity: k*(n+3) of the largest call, and k
     Fr* stage = nullptr;     // max(5k*(n+3), k*m) staging for commits/NTTs
+    uint64_t stage_elems = 0;
     uint64_t* canon = nullptr;  // canonical scalars for the fused MSM
     Fr* coset_in = nullptr;  // 7k*(n+3) coefficient staging for the coset batch
     Fr* coset_out = nullptr; // 7k*m coset evaluations (5 wires + z + PI per proof)
@@ -1636,96 +1653,39 @@ struct CohortScratch {  // per-thread device scratch for cohort proving
 static thread_local std::unique_ptr<CohortScratch> tls_cohort_scratch;
 
 static int cohort_scratch_ensure(uint64_t n, uint64_t k) {
-    if (tls_cohort_scratch && tls_cohort_scratch->n >= n && tls_cohort_scratch->k >= k)
+    // Every buffer is linear in e = k*(n+3) (k*m = 8kn < 8e), bar the two
+    // that are linear in k.  Grow each capacity to the max of old and new: a
+    // mixed-circuit stream (service batcher: n=4096 settlements between
+    // n=16384 validities) would otherwise thrash reallocations between
+    // shapes, and the scratch stays bounded by the largest single call (one
+    // n=2^17 proof, then 128 at n=4096, is not 128 x 2^17).
+    uint64_t e = k * (n + 3);
+    if (tls_cohort_scratch && tls_cohort_scratch->elems >= e && tls_cohort_scratch->k >= k)
         return RNG_OK;
-    // grow to the max of old/new in BOTH dimensions: a mixed-circuit stream
-    // (service batcher: n=4096 settlements between n=16384 validities)
-    // would otherwise thrash reallocations between shapes
     if (tls_cohort_scratch) {
-        if (tls_cohort_scratch->n > n) n = tls_cohort_scratch->n;
+        if (tls_cohort_scratch->elems > e) e = tls_cohort_scratch->elems;
         if (tls_cohort_scratch->k > k) k = tls_cohort_scratch->k;
     }
-    uint64_t m = 8 * n;
+    const uint64_t km = 8 * e;
     tls_cohort_scratch = std::make_unique<CohortScratch>();
     CohortScratch* s = tls_cohort_scratch.get();
-    uint64_t stage_elems = 5 * k * (n + 3);
-    if (stage_elems < k * m) stage_elems = k * m;
+    uint64_t stage_elems = 5 * e;
+    if (stage_elems < km) stage_elems = km;
     HIP_CHECK(hipMalloc(&s->stage, stage_elems * sizeof(Fr)));
     HIP_CHECK(hipMalloc(&s->canon, stage_elems * 4 * 8));
-    HIP_CHECK(hipMalloc(&s->coset_in, 7 * k * (n + 3) * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->coset_out, 7 * k * m * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->q_all, k * m * sizeof(Fr)));
-    HIP_CHECK(hipMalloc(&s->ntt_tmp, 7 * k * m * sizeof(Fr)));
+    HIP_CHECK(hipMalloc(&s->coset_in, 7 * e * sizeof(Fr)));
+    HIP_CHECK(hipMalloc(&s->coset_out, 7 * km * sizeof(Fr)));
+    HIP_CHECK(hipMalloc(&s->q_all, km * sizeof(Fr)));
+    HIP_CHECK(hipMalloc(&s->ntt_tmp, 7 * km * sizeof(Fr)));
     HIP_CHECK(hipMalloc(&s->chs, k * sizeof(QuotChal)));
     HIP_CHECK(hipMalloc(&s->blinders, 14 * k * sizeof(Fr)));
-    s->n = n;
+    s->stage_elems = stage_elems;
+    s->elems = e;
     s->k = k;
     return RNG_OK;
 }
 
-static int commit_staged(RngCtxImpl* ctx, uint64_t m, uint32_t B, G1Aff* out,
-                         bool* out_inf);
-
-// Fused commitment of B host polynomials (any B; shorter polys zero-padded
-// to the longest) through ONE msm_dev_run.  Host window fold + affine
-// conversion are parallelized across the pool for large B.
-static int commit_cohort(RngCtxImpl* ctx, const std::vector<Fr>* const* polys,
-                         uint32_t B, G1Aff* out, bool* out_inf) {
-    const int trace = prover_env().cohort_trace;
-    auto tr = [&](const char* tag) {
-        if (trace) {
-            fprintf(stderr, "[commit_cohort B=%u] %s\n", B, tag);
-            fflush(stderr);
-        }
-    };
-    auto tr_msm_stages = [&] {
-        if (trace)
-            fprintf(stderr,
-                    "[commit_cohort B=%u] msm stages ms: digits %.2f sort %.2f "
-                    "bucket %.2f chunks %.2f final %.2f\n",
-                    B, tls_msm_times[0], tls_msm_times[1], tls_msm_times[2],
-                    tls_msm_times[3], tls_msm_times[4]);
-    };
-    tr("enter");
-    CohortScratch* s = tls_cohort_scratch.get();
-    uint64_t m = 0;
-    for (uint32_t b = 0; b < B; ++b)
-        if (polys[b]->size() > m) m = polys[b]->size();
-    if (m > ctx->srs_count) return RNG_ERR_BAD_ARG;
-    // pack on the host (pool) and ship ONE H2D copy: B small async copies of
-    // pageable memory each pay a staging round trip.  Plain local (NOT
-    // thread_local): pool workers reference it from their own threads.
-    std::vector<Fr> packed(B * m);
-    HostPool::inst().parallel_for(B, [&](uint32_t b) {
-        memcpy(packed.data() + (size_t)b * m, polys[b]->data(),
-               polys[b]->size() * sizeof(Fr));
-        memset(packed.data() + (size_t)b * m + polys[b]->size(), 0,
-               (m - polys[b]->size()) * sizeof(Fr));
-    });
-    HIP_CHECK(hipMemcpyAsync(s->stage, packed.data(), B * m * sizeof(Fr),
-                             hipMemcpyHostToDevice, RNG_STREAM));
-    tr("msm");
-    int rc = commit_staged(ctx, m, B, out, out_inf);
-    tr("msm-done");
-    tr_msm_stages();
-    return rc;
-}
-
-// commit B polynomials that are ALREADY staged on device in s->stage
-// (B consecutive m-coefficient blocks, Montgomery form)
-static int commit_staged(RngCtxImpl* ctx, uint64_t m, uint32_t B, G1Aff* out,
-                         bool* out_inf) {
-    CohortScratch* s = tls_cohort_scratch.get();
-    if (m > ctx->srs_count) return RNG_ERR_BAD_ARG;
-    std::vector<G1Jac> res(B);
-    int rc = commit_staged_jac(ctx, s->stage, s->canon, m, B, res.data());
-    if (rc != RNG_OK) return rc;
-    HostPool::inst().parallel_for(
-        B, [&](uint32_t b) { jac_to_affine(res[b], &out[b], &out_inf[b]); });
-    return RNG_OK;
-}
-
-// round-1 commit on the Lagrange path: s->canon already holds B blocks of
+// round-1 commit on the Lagrange path: d_canon already holds B blocks of
 // n + 2 canonical scalars (k_lagrange_scalars).  MSM_LAGRANGE_UNUSABLE tells
 // the caller to commit the staged coefficients instead.
 static int commit_lagrange_canon(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon,
@@ -1733,11 +1693,7 @@ static int commit_lagrange_canon(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_
     std::vector<G1Jac> res(B);
     int rc = msm_lagrange_run(ctx, n, d_canon, B, res.data());
     if (rc != RNG_OK) return rc;
-    auto one = [&](uint32_t b) { jac_to_affine(res[b], &out[b], &out_inf[b]); };
-    if (B >= 8)
-        HostPool::inst().parallel_for(B, one);
-    else
-        for (uint32_t b = 0; b < B; ++b) one(b);
+    jacs_to_affine(res.data(), B, out, out_inf);
     return RNG_OK;
 }
 
@@ -1766,15 +1722,14 @@ static void quot_chal_set(QuotChal& ch, const ProofState& st) {
     ch.alpha2 = st.alpha.sqr();
 }
 
-// k proofs in lockstep under ONE proving key (the headline shape: a stream
-// of same-circuit jobs).  Bit-identical to k calls of plonk_prove_impl with
-// the same seeds by construction: both fill a ProofState per proof and run
-// the shared host rounds of plonk_rounds.hpp on it.  4 fused MSM runs per
-// cohort instead of 5k.
-static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint32_t k,
-                                   const Fr* wires_all, const Fr* pubs_all,
-                                   const uint64_t* seeds, uint64_t* out_proofs,
-                                   uint64_t* out_hints) {
+// k >= 1 proofs in lockstep under ONE proving key (the headline shape: a
+// stream of same-circuit jobs); the only prover, behind rng_prove (k = 1) and
+// rng_prove_cohort.  One ProofState per proof runs the shared host rounds of
+// plonk_rounds.hpp, so a proof's bytes do not depend on k.  4 fused MSM runs
+// per cohort instead of 5k.
+static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint32_t k,
+                            const Fr* wires_all, const Fr* pubs_all, const uint64_t* seeds,
+                            uint64_t* out_proofs, uint64_t* out_hints) {
     const uint64_t n = pk.n;
     const uint32_t m = (uint32_t)(8 * n);
     const uint64_t hint_u64s = 4 * (n + 2) + 9;
@@ -1797,13 +1752,12 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
     HostPool& pool = HostPool::inst();
     Fr w = h_fr_root_of_unity((uint32_t)n);
     const bool z_dev =
-        ProverEnv::on(prover_env().z_device, Z_DEVICE_DEFAULT_COHORT) && n <= PERM_MAX_N;
+        ProverEnv::on(prover_env().z_device, Z_DEVICE_DEFAULT) && n <= PERM_MAX_N;
     // R4 + R5 on the device: the blinded polynomials stay on the device (the
     // wires and z as plain coefficients in coset_in, the chunks in stage) and
     // only wire 0 comes down, for a link hint
     const bool open_on =
-        ProverEnv::on(prover_env().open_device, OPEN_DEVICE_DEFAULT_COHORT) &&
-        n <= OPEN_MAX_N;
+        ProverEnv::on(prover_env().open_device, OPEN_DEVICE_DEFAULT) && n <= OPEN_MAX_N;
 
     std::vector<ProofState> st;
     st.reserve(k);
@@ -1817,7 +1771,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         return h;
     };
 
-    // scratch for commit outputs (bool arrays for commit_cohort)
+    // one round's commitments, before the states take them
     std::vector<G1Aff> cbuf(5 * (size_t)k);
     std::unique_ptr<bool[]> ibuf(new bool[5 * (size_t)k]);
     std::vector<const std::vector<Fr>*> ps(5 * (size_t)k);
@@ -1844,7 +1798,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
                                  blind_h.size() * sizeof(Fr), hipMemcpyHostToDevice,
                                  RNG_STREAM));
         const bool lagrange =
-            ProverEnv::on(prover_env().r1_lagrange, R1_LAGRANGE_DEFAULT_COHORT);
+            ProverEnv::on(prover_env().r1_lagrange, k >= R1_LAGRANGE_MIN_K);
         if (lagrange) {
             // the commitment MSM reads the (sparse) evaluations and the
             // blinders as scalars against the Lagrange bases: canonicalise
@@ -1883,7 +1837,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
                                                    ibuf.get())
                            : MSM_LAGRANGE_UNUSABLE;
         if (crc == MSM_LAGRANGE_UNUSABLE)  // coefficient path
-            crc = commit_staged(ctx, n + 2, 5 * k, cbuf.data(), ibuf.get());
+            crc = commit_staged(ctx, cs->stage, cs->canon, n + 2, 5 * k, cbuf.data(), ibuf.get());
         if (crc != RNG_OK) return RNG_ERR_HIP;
         pool.parallel_for(k, [&](uint32_t p) {
             if (open_on) {
@@ -1965,7 +1919,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         if (!open_on)
             HIP_CHECK(hipMemcpyAsync(z_host.data(), cs->stage, totz * sizeof(Fr),
                                      hipMemcpyDeviceToHost, RNG_STREAM));
-        if (commit_staged(ctx, n + 3, k, cbuf.data(), ibuf.get()) != RNG_OK)
+        if (commit_staged(ctx, cs->stage, cs->canon, n + 3, k, cbuf.data(), ibuf.get()) != RNG_OK)
             return RNG_ERR_HIP;
         // commit_staged synchronized: z_host is complete
         pool.parallel_for(k, [&](uint32_t p) {
@@ -2051,7 +2005,7 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
             HIP_CHECK(hipMemcpyAsync(chunks_host.data(), cs->stage,
                                      total_c * sizeof(Fr), hipMemcpyDeviceToHost,
                                      RNG_STREAM));
-        if (commit_staged(ctx, n + 3, 5 * k, cbuf.data(), ibuf.get()) != RNG_OK)
+        if (commit_staged(ctx, cs->stage, cs->canon, n + 3, 5 * k, cbuf.data(), ibuf.get()) != RNG_OK)
             return RNG_ERR_HIP;
         if (!open_on)
             pool.parallel_for(k, [&](uint32_t p) {
@@ -2076,11 +2030,9 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
         const OpenSrc src{cs->coset_in, 7 * (n + 3), cs->stage, 5 * (n + 3)};
         int orc = open_dev(pk, w, src, k, st.data(), cs->q_all, cs->ntt_tmp);
         if (orc != RNG_OK) return orc;
-        std::vector<G1Jac> res(2 * (size_t)k);
-        if (n + 2 > ctx->srs_count ||
-            commit_staged_jac(ctx, cs->ntt_tmp, cs->canon, n + 2, 2 * k, res.data()) != RNG_OK)
+        if (commit_staged(ctx, cs->ntt_tmp, cs->canon, n + 2, 2 * k, cbuf.data(),
+                          ibuf.get()) != RNG_OK)
             return RNG_ERR_HIP;
-        pool.parallel_for(2 * k, [&](uint32_t b) { jac_to_affine(res[b], &cbuf[b], &ibuf[b]); });
     } else {
         std::vector<std::vector<Fr>> Wz(k), Wzw(k);
         pool.parallel_for(k, [&](uint32_t p) { rounds_4_5(pk, w, st[p], Wz[p], Wzw[p]); });
@@ -2088,7 +2040,8 @@ static int plonk_prove_cohort_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint3
             ps[2 * (size_t)p] = &Wz[p];
             ps[2 * (size_t)p + 1] = &Wzw[p];
         }
-        if (commit_cohort(ctx, ps.data(), 2 * k, cbuf.data(), ibuf.get()) != RNG_OK)
+        if (commit_host_polys(ctx, ps.data(), 2 * k, cs->stage, cs->canon, cs->stage_elems,
+                              cbuf.data(), ibuf.get()) != RNG_OK)
             return RNG_ERR_HIP;
     }
     pool.parallel_for(k, [&](uint32_t p) {
@@ -2134,21 +2087,6 @@ static int ifft_columns(RngCtxImpl* ctx, const Fr* host_evals, uint64_t n,
     }
     hipFree(d);
     return rc;
-}
-
-// same for evals ALREADY on the device: d_in (n*ncols, clobbered) through
-// the inverse NTT into d_out (n*ncols), columns downloaded to the host
-static int ifft_columns_dev(RngCtxImpl* ctx, Fr* d_in, Fr* d_out, uint64_t n,
-                            uint64_t ncols, std::vector<Fr>* out_cols) {
-    int rc = ntt_dev_run(ctx, d_in, d_out, (uint32_t)n, ncols, true, RNG_STREAM);
-    if (rc != RNG_OK) return rc;
-    for (uint64_t c = 0; c < ncols; ++c) {
-        out_cols[c].resize(n);
-        HIP_CHECK(hipMemcpyAsync(out_cols[c].data(), d_out + c * n, n * sizeof(Fr),
-                                 hipMemcpyDeviceToHost, RNG_STREAM));
-    }
-    HIP_CHECK(hipStreamSynchronize(RNG_STREAM));
-    return RNG_OK;
 }
 
 static int plonk_preprocess_impl(RngCtxImpl* ctx, const RngCircuitDesc* d,
@@ -2225,189 +2163,6 @@ static int plonk_preprocess_impl(RngCtxImpl* ctx, const RngCircuitDesc* d,
             return RNG_ERR_HIP;
     }
     HIP_CHECK(hipDeviceSynchronize());
-    return RNG_OK;
-}
-
-// One proof on the per-proof path.  Host rounds: plonk_rounds.hpp, shared
-// with the cohort prover and the verifier.
-static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, const Fr* wires,
-                            const Fr* pubs, uint64_t seed, uint64_t* out_proof,
-                            uint64_t* out_link_hint) {
-    const uint64_t n = pk.n;
-    const uint32_t m = (uint32_t)(8 * n);
-    if (prove_scratch_ensure(n) != RNG_OK) return RNG_ERR_HIP;
-    ProveScratch* sc = tls_prove_scratch.get();
-    ProofState st(pk, pubs, seed);
-    Fr w = h_fr_root_of_unity((uint32_t)n);
-    G1Aff cbuf[5];  // one round's commitments, before the state takes them
-    bool ibuf[5];
-
-    // --- R1: wire polys ---
-    std::vector<Fr>* wpoly = st.wpoly;
-    const bool z_dev =
-        ProverEnv::on(prover_env().z_device, Z_DEVICE_DEFAULT_SINGLE) && n <= PERM_MAX_N;
-    const bool lagrange =
-        ProverEnv::on(prover_env().r1_lagrange, R1_LAGRANGE_DEFAULT_SINGLE);
-    if (z_dev || lagrange) {
-        // the wire evaluations go up once and stay in w_coset (free until
-        // R3) for the device grand product and the Lagrange commit; the
-        // IFFT runs on a copy
-        Fr* wev = sc->w_coset;
-        HIP_CHECK(hipMemcpyAsync(wev, wires, 5 * n * sizeof(Fr), hipMemcpyHostToDevice,
-                                 RNG_STREAM));
-        HIP_CHECK(hipMemcpyAsync(sc->q_buf, wev, 5 * n * sizeof(Fr),
-                                 hipMemcpyDeviceToDevice, RNG_STREAM));
-        if (ifft_columns_dev(ctx, sc->q_buf, sc->tmp, n, 5, wpoly) != RNG_OK)
-            return RNG_ERR_HIP;
-    } else if (ifft_columns(ctx, wires, n, 5, wpoly) != RNG_OK) {
-        return RNG_ERR_HIP;
-    }
-    for (int j = 0; j < 5; ++j) {
-        const Fr b0 = st.blind[BLIND_WIRES + 2 * j], b1 = st.blind[BLIND_WIRES + 2 * j + 1];
-        wpoly[j].resize(n + 2, Fr::zero());
-        wpoly[j][0] = wpoly[j][0].sub(b0);
-        wpoly[j][1] = wpoly[j][1].sub(b1);
-        wpoly[j][n] = wpoly[j][n].add(b0);
-        wpoly[j][n + 1] = wpoly[j][n + 1].add(b1);
-    }
-    {
-        int crc = MSM_LAGRANGE_UNUSABLE;
-        if (lagrange) {
-            // commit the evaluations (still in w_coset) and the blinders
-            // against the Lagrange bases: same group elements
-            HIP_CHECK(hipMemcpyAsync(sc->stage, st.blind + BLIND_WIRES, 10 * sizeof(Fr),
-                                     hipMemcpyHostToDevice, RNG_STREAM));
-            uint64_t lt = 5 * (n + 2);
-            hipLaunchKernelGGL(k_lagrange_scalars, dim3((uint32_t)((lt + 255) / 256)),
-                               dim3(256), 0, RNG_STREAM, (const Fr*)sc->w_coset,
-                               (const Fr*)sc->stage, (uint32_t)n, lt, sc->canon);
-            HIP_CHECK(hipGetLastError());
-            crc = commit_lagrange_canon(ctx, n, sc->canon, 5, cbuf, ibuf);
-        }
-        if (crc == MSM_LAGRANGE_UNUSABLE) {  // coefficient path
-            const std::vector<Fr>* ps[5] = {&wpoly[0], &wpoly[1], &wpoly[2], &wpoly[3],
-                                            &wpoly[4]};
-            crc = commit_dev_batch(ctx, ps, 5, cbuf, ibuf);
-        }
-        if (crc != RNG_OK) return RNG_ERR_HIP;
-    }
-    st.take_comms(COMM_WIRES, 5, cbuf, ibuf);
-    if (out_link_hint) st.write_link_hint(out_link_hint);
-    st.beta = st.tr.challenge();
-    st.gamma = st.tr.challenge();
-
-    // --- R2: grand product ---
-    std::vector<Fr>& zpoly = st.zpoly;
-    if (z_dev) {
-        // device stage: terms/scans in q_buf, z evaluations in z_coset, and
-        // straight into the inverse NTT; only the n coefficients come back
-        const Fr bg[2] = {st.beta, st.gamma};
-        int rc = perm_product_dev(sc->w_coset, pk.sig_evals_dev, pk.wpow_dev, pk.k, bg, n,
-                                  1, sc->q_buf, sc->z_coset);
-        if (rc != RNG_OK) return rc;
-        if (ifft_columns_dev(ctx, sc->z_coset, sc->tmp, n, 1, &zpoly) != RNG_OK)
-            return RNG_ERR_HIP;
-    } else {
-        std::vector<Fr> zevals(n);
-        perm_product_host(pk, w, wires, st.beta, st.gamma, zevals.data());
-        if (ifft_columns(ctx, zevals.data(), n, 1, &zpoly) != RNG_OK) return RNG_ERR_HIP;
-    }
-    {
-        const Fr b2 = st.blind[BLIND_Z], b3 = st.blind[BLIND_Z + 1],
-                 b4 = st.blind[BLIND_Z + 2];
-        zpoly.resize(n + 3, Fr::zero());
-        zpoly[0] = zpoly[0].sub(b4);
-        zpoly[1] = zpoly[1].sub(b3);
-        zpoly[2] = zpoly[2].sub(b2);
-        zpoly[n] = zpoly[n].add(b4);
-        zpoly[n + 1] = zpoly[n + 1].add(b3);
-        zpoly[n + 2] = zpoly[n + 2].add(b2);
-    }
-    if (commit_dev(ctx, zpoly, cbuf, ibuf) != RNG_OK) return RNG_ERR_HIP;
-    st.take_comms(COMM_Z, 1, cbuf, ibuf);
-    st.alpha = st.tr.challenge();
-
-    // --- R3: quotient on the 8n coset (GPU) ---
-    for (int j = 0; j < 5; ++j)
-        if (coset_of_coeffs(ctx, wpoly[j], sc->w_coset + (size_t)j * m, m) != RNG_OK)
-            return RNG_ERR_HIP;
-    if (coset_of_coeffs(ctx, zpoly, sc->z_coset, m) != RNG_OK) return RNG_ERR_HIP;
-    {
-        std::vector<Fr> pie(n, Fr::zero());
-        for (uint64_t i = 0; i < pk.npub; ++i) pie[i] = pubs[i];
-        std::vector<Fr> picoef[1];
-        if (ifft_columns(ctx, pie.data(), n, 1, picoef) != RNG_OK) return RNG_ERR_HIP;
-        if (coset_of_coeffs(ctx, picoef[0], sc->pi_coset, m) != RNG_OK)
-            return RNG_ERR_HIP;
-    }
-    QuotChal ch = quot_chal_fixed(pk);
-    quot_chal_set(ch, st);
-    NttPlan* mp = get_plan(ctx, m, 1);
-    if (!mp || ensure_coset_tables(ctx, mp) != RNG_OK) return RNG_ERR_HIP;
-    {
-        uint32_t blocks = (m + 255) / 256;
-        hipLaunchKernelGGL(k_quotient, dim3(blocks), dim3(256), 0, RNG_STREAM,
-                           pk.sel_coset, pk.sig_coset, sc->w_coset, sc->z_coset,
-                           sc->pi_coset, pk.l1_coset, mp->xpow, sc->q_buf, m, ch);
-        HIP_CHECK(hipGetLastError());
-    }
-    if (coset_inv_dev(ctx, sc->q_buf, sc->tmp, m) != RNG_OK) return RNG_ERR_HIP;
-    std::vector<Fr> quot(5 * (n + 2));
-    HIP_CHECK(hipMemcpyAsync(quot.data(), sc->tmp, quot.size() * sizeof(Fr),
-                             hipMemcpyDeviceToHost, RNG_STREAM));
-    HIP_CHECK(hipStreamSynchronize(RNG_STREAM));
-    std::vector<Fr>* quot_chunks = st.quot_chunks;
-    {
-        Fr prev = Fr::zero();
-        for (int i = 0; i < 5; ++i) {
-            quot_chunks[i].assign(quot.begin() + (size_t)i * (n + 2),
-                                  quot.begin() + (size_t)(i + 1) * (n + 2));
-            Fr bnext = (i < 4) ? st.blind[BLIND_CHUNKS + i] : Fr::zero();
-            quot_chunks[i][0] = quot_chunks[i][0].sub(prev);
-            if (i < 4) {
-                quot_chunks[i].resize(n + 3, Fr::zero());
-                quot_chunks[i][n + 2] = quot_chunks[i][n + 2].add(bnext);
-            }
-            prev = bnext;
-        }
-        const std::vector<Fr>* ps[5] = {&quot_chunks[0], &quot_chunks[1], &quot_chunks[2],
-                                        &quot_chunks[3], &quot_chunks[4]};
-        if (commit_dev_batch(ctx, ps, 5, cbuf, ibuf) != RNG_OK) return RNG_ERR_HIP;
-        st.take_comms(COMM_CHUNKS, 5, cbuf, ibuf);
-    }
-    st.zeta = st.tr.challenge();
-
-    // --- R4 + R5: evaluations, linearization, openings (device stage or
-    //     host) ---
-    if (ProverEnv::on(prover_env().open_device, OPEN_DEVICE_DEFAULT_SINGLE) &&
-        n <= OPEN_MAX_N) {
-        // this path holds the blinded polynomials on the host: one packed
-        // upload of the 11 into stage (13 slots of n + 3); C and the two
-        // quotients go to q_buf, free since the inverse coset transform
-        const size_t stride = n + 3;
-        std::vector<Fr> packed(OPEN_PROOF_POLYS * stride, Fr::zero());
-        for (int j = 0; j < OPEN_PROOF_POLYS; ++j) {
-            const std::vector<Fr>& src = j < 5 ? wpoly[j] : j == 5 ? zpoly : quot_chunks[j - 6];
-            memcpy(packed.data() + j * stride, src.data(), src.size() * sizeof(Fr));
-        }
-        HIP_CHECK(hipMemcpyAsync(sc->stage, packed.data(), packed.size() * sizeof(Fr),
-                                 hipMemcpyHostToDevice, RNG_STREAM));
-        const OpenSrc src{sc->stage, 0, sc->stage + 6 * stride, 0};
-        Fr* Wd = sc->q_buf + stride;
-        int orc = open_dev(pk, w, src, 1, &st, sc->q_buf, Wd);
-        if (orc != RNG_OK) return orc;
-        G1Jac res[2];
-        if (commit_staged_jac(ctx, Wd, sc->canon, n + 2, 2, res) != RNG_OK)
-            return RNG_ERR_HIP;
-        for (int b = 0; b < 2; ++b) jac_to_affine(res[b], &cbuf[b], &ibuf[b]);
-    } else {
-        std::vector<Fr> Wz, Wzw;
-        rounds_4_5(pk, w, st, Wz, Wzw);
-        const std::vector<Fr>* ps[2] = {&Wz, &Wzw};
-        if (commit_dev_batch(ctx, ps, 2, cbuf, ibuf) != RNG_OK) return RNG_ERR_HIP;
-    }
-    st.take_comms(COMM_WZ, 2, cbuf, ibuf);
-    st.serialize(out_proof);
     return RNG_OK;
 }
 
@@ -2958,8 +2713,8 @@ int rng_prove(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wires,
     if (!gpu_ok()) return RNG_ERR_NO_GPU;
     if (!ctx || !pk || !wires || !out_proof) return RNG_ERR_BAD_ARG;
     if (pk->impl.npub > 0 && !public_inputs) return RNG_ERR_BAD_ARG;
-    return plonk_prove_impl(&ctx->impl, pk->impl, (const Fr*)wires,
-                            (const Fr*)public_inputs, seed, out_proof, out_link_hint);
+    return plonk_prove_impl(&ctx->impl, pk->impl, 1, (const Fr*)wires,
+                            (const Fr*)public_inputs, &seed, out_proof, out_link_hint);
 }
 
 int rng_prove_cohort(RngCtx* ctx, const RngProvingKey* pk, uint64_t k,
@@ -2970,18 +2725,12 @@ int rng_prove_cohort(RngCtx* ctx, const RngProvingKey* pk, uint64_t k,
     if (!ctx || !pk || !wires || !seeds || !out_proofs || k == 0 || k > 128)
         return RNG_ERR_BAD_ARG;
     if (pk->impl.npub > 0 && !public_inputs) return RNG_ERR_BAD_ARG;
-    if (k == 1)  // same bytes by construction; the per-proof path has lower
-                 // latency (fewer phase syncs) when there is nothing to fuse
-        return plonk_prove_impl(&ctx->impl, pk->impl, (const Fr*)wires,
-                                (const Fr*)public_inputs, seeds[0], out_proofs,
-                                out_link_hints);
-    return plonk_prove_cohort_impl(&ctx->impl, pk->impl, (uint32_t)k,
-                                   (const Fr*)wires, (const Fr*)public_inputs, seeds,
-                                   out_proofs, out_link_hints);
+    return plonk_prove_impl(&ctx->impl, pk->impl, (uint32_t)k, (const Fr*)wires,
+                            (const Fr*)public_inputs, seeds, out_proofs, out_link_hints);
 }
 
 // host wires (batch x 5 x n) + device tables -> host z (batch x n) through
-// perm_product_dev, the provers' own R2 call
+// perm_product_dev, the prover's own R2 call
 static int perm_product_hosted(const uint64_t* wires, const Fr* d_sigma, const Fr* d_wpow,
                                const Fr k5[5], const uint64_t* beta_gamma, uint64_t n,
                                uint64_t batch, uint64_t* out_z) {
@@ -3040,10 +2789,8 @@ int rng_perm_product_pk(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* wi
     const PlonkPkImpl& impl = pk->impl;
     const uint64_t n = impl.n;
     bool dev = mode == 1;
-    if (mode == 0)  // rng_prove_cohort sends k = 1 down the single-proof path
-        dev = ProverEnv::on(prover_env().z_device, batch == 1 ? Z_DEVICE_DEFAULT_SINGLE
-                                                              : Z_DEVICE_DEFAULT_COHORT) &&
-              n <= PERM_MAX_N;
+    if (mode == 0)
+        dev = ProverEnv::on(prover_env().z_device, Z_DEVICE_DEFAULT) && n <= PERM_MAX_N;
     if (dev)
         return perm_product_hosted(wires, impl.sig_evals_dev, impl.wpow_dev, impl.k, beta_gamma, n,
                                    batch, out_z);
@@ -3101,10 +2848,8 @@ int rng_open_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t
     const uint64_t n = impl.n;
     const size_t stride = n + 3, item = OPEN_PROOF_POLYS * stride, wlen = 2 * (n + 2);
     bool dev = mode == 1;
-    if (mode == 0)  // rng_prove_cohort sends k = 1 down the single-proof path
-        dev = ProverEnv::on(prover_env().open_device, k == 1 ? OPEN_DEVICE_DEFAULT_SINGLE
-                                                             : OPEN_DEVICE_DEFAULT_COHORT) &&
-              n <= OPEN_MAX_N;
+    if (mode == 0)
+        dev = ProverEnv::on(prover_env().open_device, OPEN_DEVICE_DEFAULT) && n <= OPEN_MAX_N;
     if (dev) {
         if (n > OPEN_MAX_N) return RNG_ERR_BAD_ARG;
         Fr* d = nullptr;  // polys | C | W

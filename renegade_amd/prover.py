@@ -176,7 +176,7 @@ class ProverCtx:
 
     def commit_lagrange(self, evals: np.ndarray, n: int, batch: int = 1, blinders=None,
                         window_c: int = 0):
-        """The provers' round-1 commitment on the Lagrange path: `batch`
+        """The prover's round-1 commitment on the Lagrange path: `batch`
         evaluation vectors of n canonical scalars each (4*n*batch u64) and,
         optionally, two canonical blinders per vector (8*batch u64).
         Returns a (batch, 9) array of affine records."""
@@ -212,7 +212,7 @@ class ProverCtx:
 
     def perm_product_pk(self, pk, wires: np.ndarray, beta_gamma: np.ndarray, n: int,
                         batch: int = 1, mode: int = 0):
-        """The provers' own round-2 call against proving key `pk` (a
+        """The prover's own round-2 call against proving key `pk` (a
         rng_preprocess handle of domain size n).  mode: Z_AUTO / Z_DEVICE /
         Z_HOST.  Returns a (batch, n, 4) array."""
         assert wires.dtype == np.uint64 and wires.size == 4 * 5 * n * batch
@@ -252,7 +252,7 @@ class ProverCtx:
 
     def open_pk(self, pk, polys: np.ndarray, points: np.ndarray, scalars: np.ndarray,
                 n: int, k: int = 1, mode: int = 0):
-        """The provers' own call for the batched opening against proving key
+        """The prover's own call for the batched opening against proving key
         `pk` (domain size n): polys k*11*(n+3) Fr (wires 0..4, z, chunks 0..4,
         zero-padded), points k*(zeta, zeta*w), scalars k*29 in the order of
         open_scalars.  mode: OPEN_AUTO / OPEN_DEVICE / OPEN_HOST.  Returns

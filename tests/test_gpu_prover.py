@@ -2,11 +2,17 @@
 (SURVEY.md §8c contract (i)), plus oracle-verifier acceptance of GPU proofs.
 """
 import ctypes
+import threading
+from pathlib import Path
 
 import numpy as np
 import pytest
 
+from tests.test_perm_product import SRS_POWER, build_circuit, declare, gen_test_ptau
+
 pytestmark = pytest.mark.gpu
+
+GOLD = Path(__file__).resolve().parent / "golden"
 
 U64P = ctypes.POINTER(ctypes.c_uint64)
 
@@ -129,7 +135,9 @@ class TestGpuProver:
 
     def test_cohort_bit_exact_vs_single(self, setup):
         """rng_prove_cohort(k) proofs (and hints) are bit-identical to k
-        independent rng_prove calls with the same seeds."""
+        independent rng_prove calls with the same seeds, and (rng_prove being
+        the cohort of one, not an implementation of its own) to the oracle
+        prover's."""
         s = setup
         lib = s["lib"]
         n, npub = int(s["n"]), int(s["npub"])
@@ -152,8 +160,55 @@ class TestGpuProver:
                 f"cohort proof {p} differs from single-proof path"
             assert np.array_equal(hints[hint_len * p:hint_len * (p + 1)], shint), \
                 f"cohort hint {p} differs"
+            orc_proof = np.zeros(157, dtype=np.uint64)
+            assert s["orc"].lib.orc_plonk_prove(ctypes.c_void_p(s["opk"]), ptr(s["wires"]),
+                                                ptr(s["pubs"]),
+                                                ctypes.c_uint64(int(seeds[p])),
+                                                ptr(orc_proof)) == 0
+            assert np.array_equal(proofs[157 * p:157 * (p + 1)], orc_proof), \
+                f"cohort proof {p} differs from the oracle prover"
         # same seed -> same proof within a cohort too
         assert np.array_equal(proofs[:157], proofs[157 * 3:157 * 4])
+
+    def test_prove_from_four_threads(self, setup):
+        """Four threads at once, three rng_prove calls each with link hints
+        and seeds of their own: all 12 proofs and hints equal the same seeds
+        proved serially afterwards (per-thread scratch and streams at k = 1
+        must not mix)."""
+        s = setup
+        seeds = [[100 + 10 * t + i for i in range(3)] for t in range(4)]
+        got = [[] for _ in range(4)]
+        rcs = []  # non-zero return codes; one ends every thread's loop
+        gate = threading.Barrier(4)
+
+        def run(t):
+            gate.wait()
+            for seed in seeds[t]:
+                if rcs:
+                    return
+                proof = np.zeros(157, dtype=np.uint64)
+                hint = np.zeros(4 * (s["n"] + 2) + 9, dtype=np.uint64)
+                rc = s["lib"].rng_prove(s["ctx"].h, ctypes.c_void_p(s["pk"]),
+                                        ptr(s["wires"]), ptr(s["pubs"]), seed, ptr(proof),
+                                        ptr(hint))
+                if rc != 0:
+                    rcs.append((t, seed, rc))
+                    return
+                got[t].append((proof, hint))
+
+        threads = [threading.Thread(target=run, args=(t,), daemon=True) for t in range(4)]
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join(timeout=120)
+        assert not any(th.is_alive() for th in threads), "a proving thread did not finish"
+        assert not rcs, f"rng_prove failed (thread, seed, rc): {rcs}"
+        for t in range(4):
+            assert len(got[t]) == 3
+            for seed, (proof, hint) in zip(seeds[t], got[t]):
+                serial, shint = gpu_prove(s, seed=seed, with_hint=True)
+                assert np.array_equal(proof, serial), f"thread {t} seed {seed}: proof"
+                assert np.array_equal(hint, shint), f"thread {t} seed {seed}: hint"
 
     def test_link_hint(self, setup):
         s = setup
@@ -447,4 +502,48 @@ def test_cohort_distinct_witnesses(orc):
     assert lib.rng_verify(ctx.h, ctypes.c_void_p(pk), ptr(tables[0]["pubs"]),
                           ptr(proof2)) != 0
     lib.rng_pk_free(ctypes.c_void_p(pk))
+    ctx.close()
+
+
+def test_shape_changes_on_one_thread():
+    """One thread, one context: a settlement proof (n = 4096, k = 1), a cohort
+    of 5 on the small circuit, the settlement proof again.  The prover's
+    scratch regrows in both directions (larger n with smaller k, then smaller
+    n with larger k); the first and third proofs are the committed fixture and
+    the cohort's proofs equal rng_prove at the same seeds."""
+    from renegade_amd import load_prover
+    plib = load_prover()
+    if not plib.gpu_available:
+        pytest.skip("no GPU")
+    lib = plib.lib
+    declare(lib)
+    ctx = plib.init(gen_test_ptau(lib, SRS_POWER), (1 << SRS_POWER) + 2)
+    small = build_circuit(lib, ctx, "test")
+    settle = build_circuit(lib, ctx, "settlement")
+    assert settle["n"] == 4096 and small["n"] < 4096
+
+    def prove(c, seed):
+        proof = np.zeros(157, dtype=np.uint64)
+        assert lib.rng_prove(ctx.h, ctypes.c_void_p(c["pk"]), ptr(c["wires"]),
+                             ptr(c["pubs"]), seed, ptr(proof), None) == 0
+        return proof
+
+    first = prove(settle, 7)
+    k = 5
+    seeds = np.array([41, 42, 43, 44, 45], dtype=np.uint64)
+    proofs = np.zeros(157 * k, dtype=np.uint64)
+    rc = lib.rng_prove_cohort(ctx.h, ctypes.c_void_p(small["pk"]), k,
+                              ptr(np.tile(small["wires"], k)),
+                              ptr(np.tile(small["pubs"], k)), ptr(seeds), ptr(proofs), None)
+    assert rc == 0, f"rng_prove_cohort rc={rc}"
+    third = prove(settle, 7)
+    # circuit seed 42, blinder seed 7: the fixture of tests/test_golden.py
+    gold = np.load(GOLD / "settlement_proof_cseed42_bseed7.npy")
+    assert np.array_equal(first, gold), "first settlement proof != fixture"
+    assert np.array_equal(third, gold), "settlement proof after the cohort != fixture"
+    for p in range(k):
+        assert np.array_equal(proofs[157 * p:157 * (p + 1)], prove(small, int(seeds[p]))), \
+            f"cohort proof {p} differs from rng_prove"
+    for c in (small, settle):
+        lib.rng_pk_free(ctypes.c_void_p(c["pk"]))
     ctx.close()
