@@ -125,9 +125,12 @@ int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,
 /* Batched MSM against the context's SRS, through the same call the prover's
  * commitments use: B polynomials of n CANONICAL scalars each (host, B*n*4
  * u64) against the first n SRS points.  window_c in [8,16], 0 = auto.
- * mode 0 = auto (fixed-base window table where one is allowed, else
- * windowed), 1 = fixed-base (error if no table can be built), 2 = windowed
- * variable-base Pippenger.  out = B affine records of 9 u64. */
+ * mode 0 = auto (the direct-lookup sum where it is the default and a lookup
+ * table fits its budget, else the fixed-base window table where one is
+ * allowed, else windowed), 1 = fixed-base bucket pipeline (error if no table
+ * can be built), 2 = windowed variable-base Pippenger, 3 = direct-lookup sum
+ * (window_c in [8,10] or 0; error if no lookup table fits).  out = B affine
+ * records of 9 u64. */
 int rng_msm_srs_batch(RngCtx* ctx, const uint64_t* scalars, uint64_t n, uint32_t B,
                       int window_c, int mode, uint64_t* out9xB);
 

@@ -16,6 +16,7 @@
 //  3. k_lagrange_scalars: canonical evaluations + blinders at stride n+2.
 #include <hip/hip_runtime.h>
 #include "gpu_curve.hpp"
+#include "msm_digits.hpp"
 
 namespace rng {
 
@@ -124,25 +125,9 @@ __global__ __launch_bounds__(64) void k_g1_normalize(const G1Jac* pts, uint32_t 
 template <typename F>
 __device__ inline void msm_signed_digits(const uint64_t s[4], uint32_t c, uint32_t W, F f) {
     uint32_t carry = 0;
-    uint32_t half = 1u << (c - 1);
-    uint64_t cmask = (1ull << c) - 1;
     for (uint32_t w = 0; w < W; ++w) {
-        uint32_t bit0 = w * c;
-        uint32_t limb = bit0 >> 6, off = bit0 & 63;
-        uint64_t raw = limb < 4 ? s[limb] >> off : 0;
-        if (off + c > 64 && limb + 1 < 4) raw |= s[limb + 1] << (64 - off);
-        raw = (raw & cmask) + carry;
-        uint32_t mag, sign;
-        if (raw > half) {  // negative digit raw - 2^c, carry into the next window
-            mag = (uint32_t)((1ull << c) - raw);
-            sign = 1;
-            carry = 1;
-        } else {  // raw == half stays +half, no carry
-            mag = (uint32_t)raw;
-            sign = 0;
-            carry = 0;
-        }
-        if (mag) f(w, mag, sign);
+        MsmDigit d = msm_recode_digit(s, c, w, carry);
+        if (d.mag) f(w, d.mag, d.sign);
     }
 }
 

@@ -34,12 +34,25 @@
 // The variable-base pipeline above is unchanged and still serves
 // caller-supplied bases (rng_msm_g1*), RNG_MSM_FIXED=0 and window sizes with
 // no table.
+//
+// Direct-lookup mode (dense SRS commitments): one step further,
+// k_msm_lookup_table stores every digit multiple
+// L[((w*N + i) << (c-1)) + d-1] = d * 2^(c*w) * P_i, d = 1..2^(c-1), built
+// from T for the same c, and k_msm_lookup_sum adds the n*W looked-up points
+// of a polynomial with their signs: no keys, no sort, no buckets, no
+// aggregation, one partial per 256-lane block, folded on the host.  The add
+// count is the bucket pipeline's n*W(c); the cost is W*N*2^(c-1)*64 B of
+// device memory behind a byte budget (msm_lookup_table in prover_api.hip),
+// c in {8, 9, 10}.  Every fixed-base path cuts a scalar with the one
+// msm_recode_digit of msm_digits.hpp.  The compacted Lagrange round, a
+// context whose table does not fit, and RNG_MSM_LOOKUP=0 keep the buckets.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include "gpu_curve.hpp"
+#include "msm_digits.hpp"
 
 namespace rng {
 
@@ -190,27 +203,11 @@ __global__ __launch_bounds__(256) void k_msm_digits_fixed(const uint64_t* scalar
     s[2] = scalars[4 * idx + 2];
     s[3] = scalars[4 * idx + 3];
     uint32_t carry = 0;
-    uint32_t half = 1u << (c - 1);
-    uint64_t cmask = (1ull << c) - 1;
     for (uint32_t w = 0; w < W; ++w) {
-        uint32_t bit0 = w * c;
-        uint32_t limb = bit0 >> 6, off = bit0 & 63;
-        uint64_t raw = limb < 4 ? s[limb] >> off : 0;
-        if (off + c > 64 && limb + 1 < 4) raw |= s[limb + 1] << (64 - off);
-        raw = (raw & cmask) + carry;
-        uint32_t mag, sign;
-        if (raw > half) {  // negative digit raw - 2^c, carry into the next window
-            mag = (uint32_t)((1ull << c) - raw);
-            sign = 1;
-            carry = 1;
-        } else {  // raw == half stays +half, no carry
-            mag = (uint32_t)raw;
-            sign = 0;
-            carry = 0;
-        }
+        MsmDigit d = msm_recode_digit(s, c, w, carry);
         uint64_t o = ((uint64_t)b * W + w) * n + i;
-        keys[o] = mag == 0 ? (B << c) : ((b << c) | mag);
-        vals[o] = (sign << 31) | (w * N + i);
+        keys[o] = d.mag == 0 ? (B << c) : ((b << c) | d.mag);
+        vals[o] = (d.sign << 31) | (w * N + i);
     }
     // carry out of the top window is zero: scalars < 2^254 <= 2^(W*c-1)
 }
@@ -490,6 +487,111 @@ __global__ __launch_bounds__(64) void k_msm_window_combine2(
 // (The final fold across windows — W*SUBB <= 512 Jacobians, ~1.5 KB — is
 // done on the HOST: a single-lane dependent EC chain runs ~50x slower on a
 // GPU SIMT lane than on a host core, and the data is tiny.)
+
+// ---- direct-lookup fixed-base path ----
+// The SRS is fixed for the life of a context, so the precomputation goes one
+// step past the window table: every digit multiple of every table point,
+//   L[((w*N + i) << (c-1)) + (d-1)] = d * 2^(c*w) * P_i,  d = 1 .. 2^(c-1),
+// affine, 64 B each.  A commitment is then a plain signed sum of the n*W
+// gathered points: nothing is sorted, bucketed or aggregated, and nothing is
+// read back before the block partials.  Memory W*N*2^(c-1)*64 B, behind the
+// budget of msm_lookup_table (prover_api.hip).
+
+// entries normalised behind one field inversion; the two Fq arrays are what
+// k_msm_fixed_table keeps per lane
+constexpr uint32_t MSM_LOOKUP_BATCH = MSM_FIXED_MAX_W;
+// window sizes with a lookup table; 2^(c-1) >= 128 is a multiple of the batch
+constexpr uint32_t MSM_LOOKUP_MIN_C = 8, MSM_LOOKUP_MAX_C = 10;
+
+// table build: one lane per row (w, i) of the window table `fixed` walks
+// d = 1 .. 2^(c-1) by repeated mixed add of the row's point (d = 1 is the
+// identity branch of madd, d = 2 its doubling branch), parks (X, Y) in the
+// slot and normalises MSM_LOOKUP_BATCH entries at a time.  Bases have prime
+// order r and d < r, so no multiple is the identity and every Z inverts.
+__global__ __launch_bounds__(256) void k_msm_lookup_table(const G1Aff* fixed, uint64_t rows,
+                                                          uint32_t c, G1Aff* table) {
+    uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const uint32_t nd = 1u << (c - 1);
+    const G1Aff P = fixed[r];
+    G1Aff* row = table + (r << (c - 1));
+    Fq zs[MSM_LOOKUP_BATCH], pref[MSM_LOOKUP_BATCH];  // pref[j] = Z_0 * ... * Z_j
+    G1Jac acc = G1Jac::identity();
+    for (uint32_t d0 = 0; d0 < nd; d0 += MSM_LOOKUP_BATCH) {
+        Fq run = Fq::one();
+        for (uint32_t j = 0; j < MSM_LOOKUP_BATCH; ++j) {
+            acc = acc.madd(P);  // (d0 + j + 1) * P
+            G1Aff parked;
+            parked.x = acc.X;
+            parked.y = acc.Y;
+            row[d0 + j] = parked;
+            zs[j] = acc.Z;
+            run = run.mul(acc.Z);
+            pref[j] = run;
+        }
+        Fq inv = run.inverse();
+        for (int j = (int)MSM_LOOKUP_BATCH - 1; j >= 0; --j) {
+            Fq zinv = j ? inv.mul(pref[j - 1]) : inv;
+            inv = inv.mul(zs[j]);
+            Fq zinv2 = zinv.sqr();
+            G1Aff p = row[d0 + j];
+            p.x = p.x.mul(zinv2);
+            p.y = p.y.mul(zinv2.mul(zinv));
+            row[d0 + j] = p;
+        }
+    }
+}
+
+// the sum: grid (blocks per poly, B), 256 lanes; lane t of block x takes the
+// scalars i = (x*per_lane + l)*256 + t, l < per_lane, of poly blockIdx.y
+// (coalesced, never across polynomials), recodes each in registers and adds
+// the looked-up multiples into one Jacobian.  The block folds its 256
+// accumulators through LDS with the full add (equal and opposite operands
+// meet here and in madd; both handle them) and writes ONE partial:
+// partials[poly * gridDim.x + x].
+__global__ __launch_bounds__(256) void k_msm_lookup_sum(const uint64_t* scalars, uint32_t n,
+                                                        uint32_t c, uint32_t W, uint32_t N,
+                                                        uint32_t per_lane, const G1Aff* table,
+                                                        G1Jac* partials) {
+    __shared__ G1Jac red[256];
+    // the scalar being cut lives in the lane's own LDS row, not in registers:
+    // with its 8 VGPRs live across madd the loop needs 176 VGPRs (2 waves per
+    // SIMD), without them 167 (3 waves), and the recoding's limb index
+    // becomes an address instead of a select chain
+    __shared__ uint64_t sc[256][4];
+    const uint32_t b = blockIdx.y;
+    const uint32_t first = blockIdx.x * per_lane * 256 + threadIdx.x;
+    uint64_t* s = sc[threadIdx.x];
+    const uint64_t wstride = (uint64_t)N << (c - 1);  // entries per window
+    G1Jac acc = G1Jac::identity();
+    for (uint32_t l = 0; l < per_lane; ++l) {
+        const uint32_t i = first + l * 256;
+        if (i >= n) break;
+        const uint64_t* sp = scalars + 4 * ((uint64_t)b * n + i);
+        const uint64_t s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
+        if (!(s0 | s1 | s2 | s3)) continue;
+        s[0] = s0;
+        s[1] = s1;
+        s[2] = s2;
+        s[3] = s3;
+        const G1Aff* row = table + ((uint64_t)i << (c - 1));  // L[w = 0][i][.]
+        uint32_t carry = 0;
+        for (uint32_t w = 0; w < W; ++w, row += wstride) {
+            const MsmDigit d = msm_recode_digit(s, c, w, carry);
+            if (d.mag == 0) continue;
+            const G1Aff p = row[d.mag - 1];
+            acc = acc.madd(p, d.sign != 0);
+        }
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t stride = 128; stride > 0; stride >>= 1) {
+        if (threadIdx.x < stride)
+            red[threadIdx.x] = red[threadIdx.x].add(red[threadIdx.x + stride]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[(uint64_t)b * gridDim.x + blockIdx.x] = red[0];
+}
 
 // ---- helpers ----
 __global__ void k_fr_to_canonical(const Fr* in, uint64_t* out, uint32_t n) {

@@ -247,6 +247,15 @@ struct RngCtxImpl {
         void* dev = nullptr;
     };
     FixedTable fixed_tables[3];
+    // direct-lookup tables L[((w*N + i) << (c-1)) + d-1] = d * 2^(c*w) * P_i
+    // for c = 8, 9, 10 (slot c - 8), built lazily under mu from the window
+    // table of the same c.  `tried` keeps a table that did not fit the budget
+    // or the free memory, or whose build failed, from being tried again.
+    struct LookupTable {
+        void* dev = nullptr;
+        bool tried = false;
+    };
+    LookupTable lookup_tables[3];
     // Lagrange bases per domain size n: n + 2 affine points
     // [L_0(tau)] .. [L_{n-1}(tau)], [tau^n] - [tau^0], [tau^(n+1)] - [tau^1],
     // and their window tables for at most two window sizes.  Built lazily
@@ -273,6 +282,7 @@ struct RngCtxImpl {
         }
         hip_free_guarded(srs_dev);
         for (auto& t : fixed_tables) hip_free_guarded(t.dev);
+        for (auto& t : lookup_tables) hip_free_guarded(t.dev);
         for (auto& kv : lagrange) {
             hip_free_guarded(kv.second.bases);
             for (auto& t : kv.second.tables) hip_free_guarded(t.dev);
@@ -452,6 +462,11 @@ struct MsmEnv {
     int subb;     // RNG_MSM_SUBB 1..256: combine sub-blocks per key group
     int seg_cap;  // RNG_MSM_SEGCAP 8..MSM_MAX_SEG: fixed-base sub-segment cap
     int debug;    // RNG_MSM_DEBUG: one stderr line per MSM
+    // direct-lookup path
+    int lookup;         // RNG_MSM_LOOKUP: 0 never, 1 wherever a table fits, -1 unset
+    int lookup_max_mb;  // RNG_MSM_LOOKUP_MAX_MB: table byte budget, default 10 GiB
+    int lookup_c;       // RNG_MSM_LOOKUP_C 8..10: the selector's window size
+    int lookup_l;       // RNG_MSM_LOOKUP_L 1..8: scalars per lane
 };
 
 static const MsmEnv& msm_env() {
@@ -462,7 +477,9 @@ static const MsmEnv& msm_env() {
         };
         return MsmEnv{get("RNG_MSM_FIXED", 1),  get("RNG_MSM_C", 0),
                       get("RNG_MSM_CHUNK", 0),  get("RNG_MSM_SUBB", 0),
-                      get("RNG_MSM_SEGCAP", 0), get("RNG_MSM_DEBUG", 0)};
+                      get("RNG_MSM_SEGCAP", 0), get("RNG_MSM_DEBUG", 0),
+                      get("RNG_MSM_LOOKUP", -1), get("RNG_MSM_LOOKUP_MAX_MB", 10240),
+                      get("RNG_MSM_LOOKUP_C", 0), get("RNG_MSM_LOOKUP_L", 0)};
     }();
     return env;
 }
@@ -940,16 +957,174 @@ static const G1Aff* msm_fixed_table(RngCtxImpl* ctx, uint32_t c) {
     return nullptr;
 }
 
+// ---- direct-lookup path over the SRS ----
+
+static uint64_t msm_lookup_bytes(uint64_t N, uint32_t c) {
+    return (((uint64_t)((256 + c - 1) / c) * N) << (c - 1)) * sizeof(G1Aff);
+}
+
+// Lookup table for window size c, built on first use from the window table
+// of the same c.  The table must fit the byte budget (10 GiB unless
+// RNG_MSM_LOOKUP_MAX_MB says otherwise: a policy, not a measurement) and half
+// of the device memory free at that moment; nullptr otherwise, and after a
+// failed allocation or build, and callers keep the bucket pipeline.  Holds
+// ctx->mu for the build and synchronizes before the pointer is published.
+static const G1Aff* msm_lookup_table(RngCtxImpl* ctx, uint32_t c) {
+    const uint64_t N = ctx->srs_count;
+    if (!ctx->srs_dev || N == 0 || c < MSM_LOOKUP_MIN_C || c > MSM_LOOKUP_MAX_C)
+        return nullptr;
+    const uint64_t bytes = msm_lookup_bytes(N, c);
+    const int max_mb = msm_env().lookup_max_mb;
+    if (max_mb <= 0 || bytes > ((uint64_t)max_mb << 20) || N >> 32) return nullptr;
+    RngCtxImpl::LookupTable& t = ctx->lookup_tables[c - MSM_LOOKUP_MIN_C];
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (t.dev || t.tried) return (const G1Aff*)t.dev;
+    }
+    const G1Aff* fixed = msm_fixed_table(ctx, c);  // takes ctx->mu itself
+    if (!fixed) return nullptr;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (t.dev || t.tried) return (const G1Aff*)t.dev;
+    t.tried = true;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 2) return nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    void* dev = nullptr;
+    if (hipMalloc(&dev, bytes) != hipSuccess) {
+        (void)hipGetLastError();  // out of memory is not an error here
+        return nullptr;
+    }
+    const uint64_t rows = (uint64_t)((256 + c - 1) / c) * N;
+    hipLaunchKernelGGL(k_msm_lookup_table, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0,
+                       RNG_STREAM, fixed, rows, c, (G1Aff*)dev);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(RNG_STREAM) != hipSuccess) {
+        hipFree(dev);
+        return nullptr;
+    }
+    if (msm_env().debug)
+        fprintf(stderr, "[msm] lookup table c=%u rows=%lu bytes=%lu build_ms=%.1f\n", c,
+                (unsigned long)rows, (unsigned long)bytes,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                    .count());
+    t.dev = dev;
+    return (const G1Aff*)dev;
+}
+
+// Where RNG_MSM_LOOKUP is unset: the paths on which the lookup sum replaces
+// the bucket pipeline, as the A/B of profiles/msm_lookup_ab.json decided.
+// Cohort = the fused rounds of a batch (B >= 16, as in msm_fixed_c); small =
+// single proofs, preprocessing, link proofs.
+constexpr bool MSM_LOOKUP_COHORT_DEFAULT = true;
+constexpr bool MSM_LOOKUP_SMALL_DEFAULT = true;
+
+static bool msm_lookup_wanted(uint32_t B) {
+    const int sw = msm_env().lookup;
+    if (sw >= 0) return sw != 0;
+    return B >= 16 ? MSM_LOOKUP_COHORT_DEFAULT : MSM_LOOKUP_SMALL_DEFAULT;
+}
+
+// The selector: the largest c in {8, 9, 10} whose table fits (fewest adds
+// per scalar), or RNG_MSM_LOOKUP_C alone.  *c_out = 0 where none does.
+static const G1Aff* msm_lookup_select(RngCtxImpl* ctx, uint32_t* c_out) {
+    const int c_env = msm_env().lookup_c;
+    uint32_t lo = MSM_LOOKUP_MIN_C, hi = MSM_LOOKUP_MAX_C;
+    if (c_env >= (int)lo && c_env <= (int)hi) lo = hi = (uint32_t)c_env;
+    for (uint32_t c = hi; c >= lo; --c)
+        if (const G1Aff* t = msm_lookup_table(ctx, c)) {
+            *c_out = c;
+            return t;
+        }
+    *c_out = 0;
+    return nullptr;
+}
+
+// Scalars per lane: 1 until the batch is large, then as many (<= 8) as keep
+// MSM_LOOKUP_MIN_LANES lanes.  256 CUs x 4 SIMDs x 3 waves x 64 = 196608
+// lanes are resident at the kernel's occupancy, and a grid below that leaves
+// wave slots empty; the headline sweep has 1 and 2 scalars per
+// lane level, 4 behind by 1.6 % and 8 by 13 %.
+constexpr uint64_t MSM_LOOKUP_MIN_LANES = 1ull << 18;
+static uint32_t msm_lookup_per_lane(uint64_t m, uint32_t B) {
+    const int l_env = msm_env().lookup_l;
+    if (l_env >= 1 && l_env <= 8) return (uint32_t)l_env;
+    uint32_t L = 1;
+    while (L < 8 && m * B / (2 * L) >= MSM_LOOKUP_MIN_LANES) L *= 2;
+    return L;
+}
+
+// block partials of the calling thread's lookup sums; a thread that only
+// ever takes this path allocates nothing else
+struct MsmLookupScratch {
+    G1Jac* partials = nullptr;
+    uint64_t cap = 0;
+    ~MsmLookupScratch() { hip_free_guarded(partials); }
+};
+static thread_local MsmLookupScratch tls_msm_lookup;
+
+// B polys of m canonical scalars (device) as plain signed sums of looked-up
+// points: ONE kernel, one D2H copy of the block partials, one synchronize.
+static int msm_lookup_run(const G1Aff* table, uint64_t N, const uint64_t* d_canon, uint64_t m,
+                          uint32_t c, G1Jac* h_result, uint32_t B,
+                          hipStream_t stream = RNG_STREAM) {
+    const uint32_t W = (256 + c - 1) / c;
+    const uint32_t L = msm_lookup_per_lane(m, B);
+    const uint32_t bpp = (uint32_t)((m + 256ull * L - 1) / (256ull * L));
+    const uint64_t np = (uint64_t)B * bpp;
+    MsmLookupScratch& s = tls_msm_lookup;
+    if (s.cap < np) {
+        hipFree(s.partials);
+        s.partials = nullptr;
+        s.cap = 0;
+        HIP_CHECK(hipMalloc(&s.partials, (np + np / 2 + 64) * sizeof(G1Jac)));
+        s.cap = np + np / 2 + 64;
+    }
+    if (msm_env().debug)
+        fprintf(stderr, "[msm] n=%lu B=%u lookup c=%u L=%u blocks=%u\n", (unsigned long)m, B, c,
+                L, bpp);
+    EvtTimer et;
+    et.mark(stream);
+    hipLaunchKernelGGL(k_msm_lookup_sum, dim3(bpp, B), dim3(256), 0, stream, d_canon,
+                       (uint32_t)m, c, W, (uint32_t)N, L, table, s.partials);
+    HIP_CHECK(hipGetLastError());
+    et.mark(stream);
+    std::vector<G1Jac> wsums((size_t)np);
+    HIP_CHECK(hipMemcpyAsync(wsums.data(), s.partials, np * sizeof(G1Jac),
+                             hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    // the whole sum reports as the bucket-reduce stage of tls_msm_times
+    double ms = 0;
+    et.collect(&ms, 1);
+    for (double& t : tls_msm_times) t = 0;
+    tls_msm_times[2] = ms;
+    MsmShape sh{};  // what msm_host_fold reads: B groups of bpp partials, no windows
+    sh.B = sh.G = B;
+    sh.W = 1;
+    sh.subb = bpp;
+    sh.c = c;
+    msm_host_fold(sh, wsums, h_result);
+    return RNG_OK;
+}
+
 // Every SRS commitment goes through here: B polys of m canonical scalars
 // each (device) against the first m SRS points.  window_c 0 = auto (the
-// RNG_MSM_C tuning override applies); mode 0 = fixed-base where a table is
-// allowed, else windowed; 1 = fixed-base or error; 2 = windowed.
+// RNG_MSM_C tuning override applies); mode 0 = the lookup sum where
+// msm_lookup_wanted and a table fits, else fixed-base where a table is
+// allowed, else windowed; 1 = fixed-base (bucket pipeline) or error;
+// 2 = windowed; 3 = lookup sum or error.
 static int msm_srs_run(RngCtxImpl* ctx, const uint64_t* d_canon, uint64_t m, uint32_t B,
                        G1Jac* res, int window_c = 0, int mode = 0) {
     if (m == 0 || m > ctx->srs_count || B == 0) return RNG_ERR_BAD_ARG;
     const int c_env = msm_env().c;
     if (window_c == 0 && c_env >= 8 && c_env <= 16) window_c = c_env;
     if (window_c != 0 && (window_c < 8 || window_c > 16)) return RNG_ERR_BAD_ARG;
+    if (mode == 3 || (mode == 0 && msm_fixed_enabled() && msm_lookup_wanted(B))) {
+        uint32_t c = (uint32_t)window_c;
+        const G1Aff* table = nullptr;
+        if (B <= 65535)  // poly = blockIdx.y
+            table = window_c ? msm_lookup_table(ctx, c) : msm_lookup_select(ctx, &c);
+        if (table) return msm_lookup_run(table, ctx->srs_count, d_canon, m, c, res, B);
+        if (mode == 3) return RNG_ERR_BAD_ARG;
+    }
     if (mode == 1 || (mode == 0 && msm_fixed_enabled())) {
         uint32_t c = window_c ? (uint32_t)window_c : msm_fixed_c(m, B);
         uint32_t gb = 1;
@@ -2538,7 +2713,7 @@ int rng_msm_g1_dev(RngCtx* ctx, const void* dev_bases, const void* dev_scalars,
 int rng_msm_srs_batch(RngCtx* ctx, const uint64_t* scalars, uint64_t n, uint32_t B,
                       int window_c, int mode, uint64_t* out9xB) {
     if (!gpu_ok()) return RNG_ERR_NO_GPU;
-    if (!ctx || !scalars || !out9xB || n == 0 || B == 0 || mode < 0 || mode > 2)
+    if (!ctx || !scalars || !out9xB || n == 0 || B == 0 || mode < 0 || mode > 3)
         return RNG_ERR_BAD_ARG;
     void* ds = nullptr;
     HIP_CHECK(hipMalloc(&ds, (uint64_t)B * n * 32));

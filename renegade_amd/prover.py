@@ -159,13 +159,13 @@ class ProverCtx:
                                         window_c), "rng_msm_g1")
         return out
 
-    MSM_AUTO, MSM_FIXED_BASE, MSM_WINDOWED = 0, 1, 2
+    MSM_AUTO, MSM_FIXED_BASE, MSM_WINDOWED, MSM_LOOKUP = 0, 1, 2, 3
 
     def msm_srs_batch(self, scalars: np.ndarray, n: int, batch: int = 1,
                       window_c: int = 0, mode: int = 0):
         """`batch` polynomials of n canonical scalars each (4*n*batch u64)
         against the first n SRS points, through the prover's own commitment
-        MSM.  mode: MSM_AUTO / MSM_FIXED_BASE / MSM_WINDOWED.  Returns a
+        MSM.  mode: MSM_AUTO / MSM_FIXED_BASE / MSM_WINDOWED / MSM_LOOKUP.  Returns a
         (batch, 9) array of affine records."""
         assert scalars.dtype == np.uint64 and scalars.size == 4 * n * batch
         scalars = np.ascontiguousarray(scalars).reshape(-1)
