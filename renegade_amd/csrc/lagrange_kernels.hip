@@ -13,7 +13,12 @@
 //     only the non-zero signed digits are written, with the key/val packing
 //     of k_msm_digits_fixed, so every later MSM stage runs on the real
 //     entry count;
-//  3. k_lagrange_scalars: canonical evaluations + blinders at stride n+2.
+//  3. k_lagrange_scalars: canonical evaluations + blinders at stride n+2;
+//  4. k_msm_entry_lookup_sum: the commitment as a plain signed sum over the
+//     compacted entries, each gathering its digit multiple from a lookup
+//     table over the bases (k_msm_lookup_table over the domain's window
+//     table), with k_msm_digit_count_density feeding it the entry offsets
+//     and the density figure in one pass.
 #include <hip/hip_runtime.h>
 #include "gpu_curve.hpp"
 #include "msm_digits.hpp"
@@ -131,6 +136,19 @@ __device__ inline void msm_signed_digits(const uint64_t s[4], uint32_t c, uint32
     }
 }
 
+// the block's sum of one flag per lane, added to *out by ONE atomic (every
+// lane of the 256-lane block calls this)
+__device__ inline void block_count_add(bool flag, uint32_t* out) {
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(flag));
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t sum = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        if (sum) atomicAdd(out, sum);
+    }
+}
+
 // counts[idx] = non-zero digits of scalar idx (idx < total_scalars = n*B)
 __global__ __launch_bounds__(256) void k_msm_digit_count(const uint64_t* scalars,
                                                          uint32_t total_scalars, uint32_t c,
@@ -143,6 +161,27 @@ __global__ __launch_bounds__(256) void k_msm_digit_count(const uint64_t* scalars
     if (s[0] | s[1] | s[2] | s[3])
         msm_signed_digits(s, c, W, [&](uint32_t, uint32_t, uint32_t) { ++cnt; });
     counts[idx] = cnt;
+}
+
+// k_msm_digit_count for the lookup sum over compacted entries: also writes
+// counts[total_scalars] = 0, so the exclusive scan over total_scalars + 1
+// words ends in the entry total and every poly's range has an upper end, and
+// adds the non-zero SCALARS (the density figure) to *nonzero, one atomic per
+// block.  The grid covers total_scalars + 1 lanes.
+__global__ __launch_bounds__(256) void k_msm_digit_count_density(
+    const uint64_t* scalars, uint32_t total_scalars, uint32_t c, uint32_t W, uint32_t* counts,
+    uint32_t* nonzero) {
+    uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t cnt = 0;
+    if (idx < total_scalars) {
+        uint64_t s[4] = {scalars[4 * idx], scalars[4 * idx + 1], scalars[4 * idx + 2],
+                         scalars[4 * idx + 3]};
+        if (s[0] | s[1] | s[2] | s[3])
+            msm_signed_digits(s, c, W, [&](uint32_t, uint32_t, uint32_t) { ++cnt; });
+    }
+    if (idx <= total_scalars) counts[idx] = cnt;
+    // a non-zero scalar has a non-zero digit
+    block_count_add(cnt != 0, nonzero);
 }
 
 // scatter after the exclusive scan of counts: key = poly << c | magnitude,
@@ -158,8 +197,8 @@ __global__ __launch_bounds__(256) void k_msm_digits_compact(
     uint32_t b = idx / n, i = idx % n;
     uint32_t o = offs[idx];
     msm_signed_digits(s, c, W, [&](uint32_t w, uint32_t mag, uint32_t sign) {
-        keys[o] = (b << c) | mag;
-        vals[o] = (sign << 31) | (w * N + i);
+        keys[o] = msm_entry_key(b, mag, c);
+        vals[o] = msm_entry_val(w, N, i, sign);
         ++o;
     });
 }
@@ -173,8 +212,50 @@ __global__ __launch_bounds__(256) void k_count_nonzero_scalars(const uint64_t* s
     if (idx < total)
         nz = (scalars[4 * idx] | scalars[4 * idx + 1] | scalars[4 * idx + 2] |
               scalars[4 * idx + 3]) != 0;
-    uint32_t cnt = (uint32_t)__popcll(__ballot(nz));
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(out, cnt);
+    block_count_add(nz, out);
+}
+
+// ---- lookup sum over compacted entries ----
+// table: L[((w*N + i) << (c-1)) + d-1] = d * 2^(c*w) * base_i over the N
+// bases of a domain (k_msm_lookup_table over the domain's window table).
+// keys/vals: the entries k_msm_digits_compact wrote; scalars lie poly-major,
+// so poly b owns the entries offs[b*N] .. offs[(b+1)*N] (offs has B*N + 1
+// words, the last one the entry total) and nothing is sorted.
+//
+// grid (S, B), 256 lanes: the lanes of block (x, b) stride over poly b's
+// range from x*256 + lane in steps of S*256, add the looked-up points into
+// one Jacobian each, and the block folds them through LDS into
+// partials[b*S + x].  Lanes past the range hold the identity and stay out
+// of the fold; a block past the range only writes the identity.  No lane
+// reads an entry outside [lo, hi).
+__global__ __launch_bounds__(256) void k_msm_entry_lookup_sum(
+    const uint32_t* keys, const uint32_t* vals, const uint32_t* offs, uint32_t N, uint32_t c,
+    const G1Aff* table, G1Jac* partials) {
+    __shared__ G1Jac red[256];
+    const uint32_t b = blockIdx.y;
+    const uint32_t lo = offs[(uint64_t)b * N], hi = offs[(uint64_t)(b + 1) * N];
+    const uint32_t first = blockIdx.x * 256;  // S <= 2^16: no overflow
+    G1Jac* out = partials + (uint64_t)b * gridDim.x + blockIdx.x;
+    if (first >= hi - lo) {  // block-uniform
+        if (threadIdx.x == 0) *out = G1Jac::identity();
+        return;
+    }
+    const uint32_t active = hi - lo - first < 256 ? hi - lo - first : 256;
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    G1Jac acc = G1Jac::identity();
+    for (uint64_t e = (uint64_t)lo + first + threadIdx.x; e < hi; e += step) {
+        const uint32_t key = keys[e], val = vals[e];
+        const G1Aff p = table[msm_lookup_index(key, val, c)];
+        acc = acc.madd(p, msm_entry_sign(val) != 0);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t stride = 128; stride > 0; stride >>= 1) {
+        if (threadIdx.x < stride && threadIdx.x + stride < active)
+            red[threadIdx.x] = red[threadIdx.x].add(red[threadIdx.x + stride]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = red[0];
 }
 
 // canonical scalars of B polys at stride n+2: the n evaluations (Montgomery

@@ -51,4 +51,38 @@ MSM_DIGIT_HD inline MsmDigit msm_recode_digit(const uint64_t s[4], uint32_t c, u
     return d;
 }
 
+// ---- compacted entries of the fixed-base paths ----
+// A non-zero digit travels as two words (k_msm_digits_fixed's packing):
+//   key = poly << c | mag          (1 <= mag <= 2^(c-1) needs c bits)
+//   val = sign << 31 | (w*N + i)   (row of the window table, N bases)
+// so the packing needs W*N < 2^31 rows.
+
+MSM_DIGIT_HD inline uint32_t msm_entry_key(uint32_t poly, uint32_t mag, uint32_t c) {
+    return (poly << c) | mag;
+}
+MSM_DIGIT_HD inline uint32_t msm_entry_val(uint32_t w, uint32_t N, uint32_t i, uint32_t sign) {
+    return (sign << 31) | (w * N + i);
+}
+MSM_DIGIT_HD inline uint32_t msm_entry_mag(uint32_t key, uint32_t c) {
+    return key & ((1u << c) - 1);
+}
+MSM_DIGIT_HD inline uint32_t msm_entry_row(uint32_t val) { return val & 0x7fffffffu; }
+MSM_DIGIT_HD inline uint32_t msm_entry_sign(uint32_t val) { return val >> 31; }
+
+// rows of the window table over N bases at window size c
+MSM_DIGIT_HD inline uint64_t msm_table_rows(uint64_t N, uint32_t c) {
+    return (uint64_t)((256 + c - 1) / c) * N;
+}
+// the row must leave bit 31 of val to the sign
+MSM_DIGIT_HD inline bool msm_entry_rows_fit(uint64_t N, uint32_t c) {
+    return msm_table_rows(N, c) < (1ull << 31);
+}
+
+// where the entry's point d * 2^(c*w) * base_i lies in the lookup table
+//   L[((w*N + i) << (c-1)) + d-1];
+// 64-bit: the product passes 2^32 long before the row count passes 2^31
+MSM_DIGIT_HD inline uint64_t msm_lookup_index(uint32_t key, uint32_t val, uint32_t c) {
+    return ((uint64_t)msm_entry_row(val) << (c - 1)) + (msm_entry_mag(key, c) - 1);
+}
+
 }  // namespace rng

@@ -261,10 +261,14 @@ struct RngCtxImpl {
     // and their window tables for at most two window sizes.  Built lazily
     // under mu; an unusable domain (a base at infinity, n + 2 > srs_count,
     // a failed build) keeps its entry so it is not tried again.
+    // lookup[c - 8]: the direct-lookup table over the domain's bases, rows
+    // (w, i) of the window table of the same c, for the sum over compacted
+    // entries; budget and `tried` as for lookup_tables.
     struct LagrangeDomain {
         bool usable = false;
         void* bases = nullptr;
         FixedTable tables[2];
+        LookupTable lookup[3];
     };
     std::map<uint64_t, LagrangeDomain> lagrange;
     uint64_t h_g2[16];       // h: x.c0,x.c1,y.c0,y.c1 Montgomery
@@ -286,6 +290,7 @@ struct RngCtxImpl {
         for (auto& kv : lagrange) {
             hip_free_guarded(kv.second.bases);
             for (auto& t : kv.second.tables) hip_free_guarded(t.dev);
+            for (auto& t : kv.second.lookup) hip_free_guarded(t.dev);
         }
     }
 };
@@ -467,6 +472,9 @@ struct MsmEnv {
     int lookup_max_mb;  // RNG_MSM_LOOKUP_MAX_MB: table byte budget, default 10 GiB
     int lookup_c;       // RNG_MSM_LOOKUP_C 8..10: the selector's window size
     int lookup_l;       // RNG_MSM_LOOKUP_L 1..8: scalars per lane
+    // lookup sum over compacted entries, round 1
+    int r1_lookup;    // RNG_R1_LOOKUP: 0 off, 1 on, -1 unset (R1_LOOKUP_DEFAULT)
+    int r1_lookup_s;  // RNG_R1_LOOKUP_S 1..64: blocks per poly
 };
 
 static const MsmEnv& msm_env() {
@@ -479,7 +487,8 @@ static const MsmEnv& msm_env() {
                       get("RNG_MSM_CHUNK", 0),  get("RNG_MSM_SUBB", 0),
                       get("RNG_MSM_SEGCAP", 0), get("RNG_MSM_DEBUG", 0),
                       get("RNG_MSM_LOOKUP", -1), get("RNG_MSM_LOOKUP_MAX_MB", 10240),
-                      get("RNG_MSM_LOOKUP_C", 0), get("RNG_MSM_LOOKUP_L", 0)};
+                      get("RNG_MSM_LOOKUP_C", 0), get("RNG_MSM_LOOKUP_L", 0),
+                      get("RNG_R1_LOOKUP", -1), get("RNG_R1_LOOKUP_S", 0)};
     }();
     return env;
 }
@@ -1275,12 +1284,226 @@ static uint32_t msm_lagrange_c(uint64_t n, uint32_t B, uint64_t nonzero) {
     return nonzero * 2 <= (uint64_t)B * n ? MSM_LAGRANGE_SPARSE_C : 0;
 }
 
+// ---- lookup sum over compacted entries ----
+// After compaction a sparse batch is a few thousand entries per poly, already
+// grouped by poly, so with every digit multiple of every base precomputed the
+// commitment is a plain signed sum: no sort, buckets, merge or combine.
+
+// RNG_R1_LOOKUP unset: as the A/B of profiles/lagrange_lookup_ab.json decided
+constexpr bool R1_LOOKUP_DEFAULT = true;
+
+static bool r1_lookup_wanted(uint32_t B) {
+    const int sw = msm_env().r1_lookup;
+    return msm_lookup_wanted(B) && (sw < 0 ? R1_LOOKUP_DEFAULT : sw == 1);
+}
+
+// Lookup table over the bases of domain n for window size c, built on first
+// use from the domain's window table of the same c.  Budget, free-memory rule
+// and `tried` as in msm_lookup_table; a row count that would reach the sign
+// bit of an entry gets no table.  Holds ctx->mu for the build and
+// synchronizes before the pointer is published.
+static const G1Aff* msm_lagrange_lookup_table(RngCtxImpl* ctx, uint64_t n, uint32_t c) {
+    if (c < MSM_LOOKUP_MIN_C || c > MSM_LOOKUP_MAX_C) return nullptr;
+    const uint64_t N = n + 2;
+    const uint64_t bytes = msm_lookup_bytes(N, c);
+    const int max_mb = msm_env().lookup_max_mb;
+    if (max_mb <= 0 || bytes > ((uint64_t)max_mb << 20) || !msm_entry_rows_fit(N, c))
+        return nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        auto it = ctx->lagrange.find(n);
+        if (it != ctx->lagrange.end()) {
+            RngCtxImpl::LookupTable& t = it->second.lookup[c - MSM_LOOKUP_MIN_C];
+            if (t.dev || t.tried || !it->second.usable) return (const G1Aff*)t.dev;
+        }
+    }
+    const G1Aff* fixed = msm_lagrange_table(ctx, n, c);  // takes ctx->mu itself
+    if (!fixed) return nullptr;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    RngCtxImpl::LookupTable& t = ctx->lagrange.find(n)->second.lookup[c - MSM_LOOKUP_MIN_C];
+    if (t.dev || t.tried) return (const G1Aff*)t.dev;
+    t.tried = true;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 2) return nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    void* dev = nullptr;
+    if (hipMalloc(&dev, bytes) != hipSuccess) {
+        (void)hipGetLastError();  // out of memory is not an error here
+        return nullptr;
+    }
+    const uint64_t rows = msm_table_rows(N, c);
+    hipLaunchKernelGGL(k_msm_lookup_table, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0,
+                       RNG_STREAM, fixed, rows, c, (G1Aff*)dev);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(RNG_STREAM) != hipSuccess) {
+        hipFree(dev);
+        return nullptr;
+    }
+    if (msm_env().debug)
+        fprintf(stderr,
+                "[msm] lagrange lookup table n=%lu c=%u rows=%lu bytes=%lu build_ms=%.1f\n",
+                (unsigned long)n, c, (unsigned long)rows, (unsigned long)bytes,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                    .count());
+    t.dev = dev;
+    return (const G1Aff*)dev;
+}
+
+// The calling thread's buffers for the sum over compacted entries; every
+// dimension grows with slack and never shrinks, so a thread that alternates
+// this path with the dense lookup sum allocates nothing per proof.
+struct R1LookupScratch {
+    uint32_t *counts = nullptr, *offs = nullptr;  // cap_scalars + 2 words each
+    uint64_t cap_scalars = 0;
+    void* scan_temp = nullptr;
+    size_t scan_temp_bytes = 0;
+    uint32_t *keys = nullptr, *vals = nullptr;
+    uint64_t cap_entries = 0;
+    G1Jac* partials = nullptr;
+    uint64_t cap_partials = 0;
+    ~R1LookupScratch() {
+        for (void* b : {(void*)counts, (void*)offs, scan_temp, (void*)keys, (void*)vals,
+                        (void*)partials})
+            hip_free_guarded(b);
+    }
+};
+static thread_local R1LookupScratch tls_r1_lookup;
+
+// grow `*buf` to hold `want` elements of `elem` bytes (contents are not kept)
+static int r1_scratch_grow(void** buf, uint64_t* cap, uint64_t want, size_t elem) {
+    if (*cap >= want) return RNG_OK;
+    hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const uint64_t ncap = want + want / 2 + 64;
+    HIP_CHECK(hipMalloc(buf, ncap * elem));
+    *cap = ncap;
+    return RNG_OK;
+}
+
+// Blocks per poly: about R1_LOOKUP_PER_LANE entries per lane at the batch's
+// mean entry count.  A lane's chain is its madds plus the block's 8 fold
+// levels, so a few entries per lane keep both short while the partials the
+// host folds stay few (settlement cohort: ~2.2 k entries per poly -> S = 3).
+constexpr uint32_t R1_LOOKUP_PER_LANE = 4, R1_LOOKUP_MAX_S = 64;
+static uint32_t r1_lookup_blocks(uint64_t entries, uint32_t B) {
+    const int s_env = msm_env().r1_lookup_s;
+    if (s_env >= 1 && s_env <= (int)R1_LOOKUP_MAX_S) return (uint32_t)s_env;
+    const uint64_t per_block = 256ull * R1_LOOKUP_PER_LANE;
+    uint64_t S = (entries / B + per_block - 1) / per_block;
+    return (uint32_t)(S < 1 ? 1 : S > R1_LOOKUP_MAX_S ? R1_LOOKUP_MAX_S : S);
+}
+
+// internal results of r1_lookup_run: the gate found the batch dense (nothing
+// was committed); the domain has no lookup table (the caller keeps the
+// bucket pipeline)
+constexpr int R1_LOOKUP_DENSE = -101, R1_LOOKUP_NO_TABLE = -102;
+
+// B blocks of n + 2 canonical scalars as a sum of looked-up points over the
+// compacted entries at window size c.  Two synchronizes: (1) digit count (+
+// the density figure where `gate`) and scan, read back as {entry total,
+// non-zero scalars}; (2) compact, sum, the S partials per poly.
+static int r1_lookup_run(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon, uint32_t B,
+                         uint32_t c, bool gate, G1Jac* h_result) {
+    const hipStream_t stream = RNG_STREAM;
+    const uint32_t N = (uint32_t)n + 2, W = (256 + c - 1) / c;
+    const uint32_t ns = B * N;
+    {  // a domain that was refused its table stays on the bucket path
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        auto it = ctx->lagrange.find(n);
+        if (it != ctx->lagrange.end()) {
+            const RngCtxImpl::LookupTable& t = it->second.lookup[c - MSM_LOOKUP_MIN_C];
+            if (!it->second.usable || (t.tried && !t.dev)) return R1_LOOKUP_NO_TABLE;
+        }
+    }
+    R1LookupScratch& s = tls_r1_lookup;
+    if (s.cap_scalars < ns) {
+        uint64_t cap_c = s.cap_scalars, cap_o = s.cap_scalars;
+        int rc = r1_scratch_grow((void**)&s.counts, &cap_c, (uint64_t)ns + 2, 4);
+        if (rc == RNG_OK) rc = r1_scratch_grow((void**)&s.offs, &cap_o, (uint64_t)ns + 2, 4);
+        s.cap_scalars = 0;
+        if (rc != RNG_OK) return rc;
+        hipFree(s.scan_temp);
+        s.scan_temp = nullptr;
+        (void)rocprim::exclusive_scan(nullptr, s.scan_temp_bytes, s.counts, s.offs, 0u, cap_c,
+                                      rocprim::plus<uint32_t>(), stream);
+        HIP_CHECK(hipMalloc(&s.scan_temp, s.scan_temp_bytes));
+        s.cap_scalars = cap_c - 2;
+    }
+    // offs[0 .. ns]: entry offsets, offs[ns] the total; offs[ns + 1]: the
+    // non-zero scalar count, so one 8-byte copy reads both
+    EvtTimer et;
+    et.mark(stream);
+    HIP_CHECK(hipMemsetAsync(s.offs + ns + 1, 0, 4, stream));
+    hipLaunchKernelGGL(k_msm_digit_count_density, dim3(ns / 256 + 1), dim3(256), 0, stream,
+                       d_canon, ns, c, W, s.counts, s.offs + ns + 1);
+    HIP_CHECK(hipGetLastError());
+    (void)rocprim::exclusive_scan(s.scan_temp, s.scan_temp_bytes, s.counts, s.offs, 0u,
+                                  (size_t)ns + 1, rocprim::plus<uint32_t>(), stream);
+    et.mark(stream);
+    uint32_t back[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(back, s.offs + ns, 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const uint64_t entries = back[0];
+    if (gate && msm_lagrange_c(n, B, back[1]) == 0) return R1_LOOKUP_DENSE;
+    const G1Aff* table = msm_lagrange_lookup_table(ctx, n, c);
+    if (!table) return R1_LOOKUP_NO_TABLE;
+    const uint32_t S = r1_lookup_blocks(entries, B);
+    if (msm_env().debug)
+        fprintf(stderr, "[msm] n=%lu B=%u entry-lookup c=%u S=%u entries=%lu (compacted)\n",
+                (unsigned long)N, B, c, S, (unsigned long)entries);
+    for (double& t : tls_msm_times) t = 0;
+    if (entries == 0) {  // every scalar zero
+        for (uint32_t b = 0; b < B; ++b) h_result[b] = G1Jac::identity();
+        et.collect(tls_msm_times, 1);
+        return RNG_OK;
+    }
+    const uint64_t np = (uint64_t)B * S;
+    int rc = r1_scratch_grow((void**)&s.partials, &s.cap_partials, np, sizeof(G1Jac));
+    if (rc != RNG_OK) return rc;
+    if (s.cap_entries < entries) {
+        uint64_t cap_k = s.cap_entries, cap_v = s.cap_entries;
+        rc = r1_scratch_grow((void**)&s.keys, &cap_k, entries, 4);
+        if (rc == RNG_OK) rc = r1_scratch_grow((void**)&s.vals, &cap_v, entries, 4);
+        s.cap_entries = rc == RNG_OK ? cap_k : 0;
+        if (rc != RNG_OK) return rc;
+    }
+    et.mark(stream);
+    hipLaunchKernelGGL(k_msm_digits_compact, dim3((ns + 255) / 256), dim3(256), 0, stream,
+                       d_canon, N, c, W, B, N, s.offs, s.keys, s.vals);
+    HIP_CHECK(hipGetLastError());
+    et.mark(stream);
+    hipLaunchKernelGGL(k_msm_entry_lookup_sum, dim3(S, B), dim3(256), 0, stream, s.keys,
+                       s.vals, s.offs, N, c, table, s.partials);
+    HIP_CHECK(hipGetLastError());
+    et.mark(stream);
+    std::vector<G1Jac> wsums((size_t)np);
+    HIP_CHECK(hipMemcpyAsync(wsums.data(), s.partials, np * sizeof(G1Jac),
+                             hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    // digits = count + scan + compact; the sum reports as the bucket-reduce
+    // stage, as msm_lookup_run's does
+    double ms[4] = {0, 0, 0, 0};  // count+scan, the read-back gap, compact, sum
+    et.collect(ms, 4);
+    tls_msm_times[0] = ms[0] + ms[2];
+    tls_msm_times[2] = ms[3];
+    MsmShape sh{};  // what msm_host_fold reads: B groups of S partials, no windows
+    sh.B = sh.G = B;
+    sh.W = 1;
+    sh.subb = S;
+    sh.c = c;
+    msm_host_fold(sh, wsums, h_result);
+    return RNG_OK;
+}
+
 // B evaluation vectors committed against the Lagrange bases of domain n:
 // d_canon holds B blocks of n + 2 canonical scalars (n evaluations, then the
 // poly's two blinders).  Same group elements as msm_srs_run over the blinded
 // coefficients.  window_c 0 = msm_lagrange_c (RNG_MSM_C overrides); where
 // that declines a dense batch the result is MSM_LAGRANGE_UNUSABLE, unless
-// dense_too (the test hook) asks for the commitment anyway.
+// dense_too (the test hook) asks for the commitment anyway.  Where the window
+// is in the lookup range and the domain has a lookup table the commitment is
+// r1_lookup_run's sum over compacted entries (two synchronizes); otherwise
+// the bucket pipeline over compacted digits, as before.
 static int msm_lagrange_run(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon, uint32_t B,
                             G1Jac* res, int window_c = 0, bool dense_too = false) {
     if (n < 2 || (n & (n - 1)) || B == 0 || !d_canon) return RNG_ERR_BAD_ARG;
@@ -1289,6 +1512,20 @@ static int msm_lagrange_run(RngCtxImpl* ctx, uint64_t n, const uint64_t* d_canon
     if (window_c == 0 && c_env >= 8 && c_env <= 16) window_c = c_env;
     if (window_c != 0 && (window_c < 8 || window_c > 16)) return RNG_ERR_BAD_ARG;
     uint32_t c = (uint32_t)window_c;
+    // the lookup sum over compacted entries, where the window the batch would
+    // get has a lookup table: the density gate rides on its digit count
+    const uint32_t c_try = c ? c : MSM_LAGRANGE_SPARSE_C;
+    if (r1_lookup_wanted(B) && c_try >= MSM_LOOKUP_MIN_C && c_try <= MSM_LOOKUP_MAX_C &&
+        B <= 65535 && msm_table_rows(n + 2, c_try) * B < (1ull << 32)) {
+        int rc = r1_lookup_run(ctx, n, d_canon, B, c_try, /*gate=*/c == 0, res);
+        if (rc != R1_LOOKUP_DENSE && rc != R1_LOOKUP_NO_TABLE) return rc;
+        if (rc == R1_LOOKUP_DENSE) {
+            if (!dense_too) return MSM_LAGRANGE_UNUSABLE;
+            c = MSM_LAGRANGE_DENSE_C;
+        } else {
+            c = c_try;  // sparse (or the caller's c), but no table: the buckets
+        }
+    }
     if (c == 0) {
         MsmScratch* s = nullptr;
         // any shape sizes the scratch; head_count doubles as the counter
