@@ -259,6 +259,29 @@ int rng_open_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t
                 const uint64_t* points, const uint64_t* scalars, int mode,
                 uint64_t* out_w);
 
+/* Test hook in the style of rng_open_pk: the SAME internal call the prover's
+ * round 3 makes between the commitment of z and the commitment of the
+ * quotient chunks, against the key's own coset tables (n = the key's domain
+ * size, m = 8n).  Per proof p: the seven polynomials are evaluated on the
+ * coset g * H_m, the numerator of plonk_kernels.hip is formed pointwise with
+ * (beta, gamma, alpha) = challenges[p], divided by Z_H, interpolated back,
+ * and split into five chunks of n+2 coefficients.  The inputs need not
+ * satisfy any circuit.
+ * host buffers, Montgomery Fr; polys = k x 7 x (n+3), slot order wires 0..4,
+ * z, PI (the public-input polynomial), each zero-padded to n+3; challenges =
+ * k x 3: beta, gamma, alpha; blinders = k x 4 chunk blinders b_0..b_3, or
+ * NULL for zeros; out_chunks = k x 5 x (n+3): chunk i holds quotient
+ * coefficients i(n+2) .. (i+1)(n+2)-1, then [0] -= b_{i-1} for i > 0 and
+ * [n+2] += b_i for i < 4 (chunk 4's slot n+2 stays zero); out_quot (optional,
+ * NULL to skip) = k x 8n: every quotient coefficient before the split, those
+ * from 5(n+2) up included, which the chunks drop.  1 <= k <= 128.
+ * mode 0 = the coset extension the prover would pick (RNG_OPEN_DEVICE, else
+ * the default, the same for every k), 1 = scale and pad out of place, 2 =
+ * scale in place, then pad. */
+int rng_quotient_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t* polys,
+                    const uint64_t* challenges, const uint64_t* blinders, int mode,
+                    uint64_t* out_chunks, uint64_t* out_quot);
+
 int rng_verify(RngCtx* ctx, const RngProvingKey* pk, const uint64_t* public_inputs,
                const uint64_t* proof);
 

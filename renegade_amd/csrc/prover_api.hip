@@ -2134,6 +2134,81 @@ static void quot_chal_set(QuotChal& ch, const ProofState& st) {
     ch.alpha2 = st.alpha.sqr();
 }
 
+// Round 3 up to the chunk commit, for k proofs: cs->coset_in holds k x 7
+// coefficient polynomials at stride n+3 (wires 0..4, z, PI) on entry; on
+// return cs->stage holds the 5k blinded chunks at stride n+3 and cs->ntt_tmp
+// the k x m quotient coefficients.  out_of_place keeps coset_in plain (the
+// device R4 + R5 read it again); otherwise it is scaled in place.  chs_h: k
+// challenge packs, qblind_h: 4k chunk blinders, both host; the caller keeps
+// qblind_h alive until its next synchronisation of RNG_STREAM.  The prover
+// and rng_quotient_pk both come through here.
+static int quotient_stage(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint32_t k,
+                          CohortScratch* cs, bool out_of_place, const QuotChal* chs_h,
+                          const Fr* qblind_h) {
+    const uint64_t n = pk.n;
+    const uint32_t m = (uint32_t)(8 * n);
+    NttPlan* mp = get_plan(ctx, m, 0);  // tables only; batch NTTs below
+    if (!mp || ensure_coset_tables(ctx, mp) != RNG_OK) return RNG_ERR_HIP;
+    const uint64_t stride = n + 3;
+    uint64_t total_in = 7 * (uint64_t)k * stride;
+    uint64_t total_m = 7 * (uint64_t)k * m;
+    if (out_of_place) {
+        // R4 + R5 read the plain coefficients again: scale while padding,
+        // out of place
+        hipLaunchKernelGGL(k_scale_pad_batch, dim3((uint32_t)((total_m + 255) / 256)),
+                           dim3(256), 0, RNG_STREAM, (const Fr*)cs->coset_in,
+                           (uint32_t)stride, (const Fr*)mp->gpow, cs->ntt_tmp, m,
+                           total_m);
+        HIP_CHECK(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(k_mul_pointwise_mod,
+                           dim3((uint32_t)((total_in + 255) / 256)), dim3(256), 0,
+                           RNG_STREAM, cs->coset_in, mp->gpow, (uint32_t)stride,
+                           total_in);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_copy_pad_batch, dim3((uint32_t)((total_m + 255) / 256)),
+                           dim3(256), 0, RNG_STREAM, cs->coset_in, (uint32_t)stride,
+                           cs->ntt_tmp, m, total_m);
+        HIP_CHECK(hipGetLastError());
+    }
+    int rc = ntt_dev_run(ctx, cs->ntt_tmp, cs->coset_out, m, 7 * (uint64_t)k, false,
+                         RNG_STREAM);
+    if (rc != RNG_OK) return rc;
+
+    // ONE batched quotient launch for all k proofs (a single proof's m
+    // grid is latency-starved; 483 small launches were 14% of cohort GPU
+    // time in the r02 profile)
+    {
+        HIP_CHECK(hipMemcpyAsync(cs->chs, chs_h, k * sizeof(QuotChal),
+                                 hipMemcpyHostToDevice, RNG_STREAM));
+        uint64_t total_kq = (uint64_t)k * m;
+        hipLaunchKernelGGL(k_quotient_batch,
+                           dim3((uint32_t)((total_kq + 255) / 256)), dim3(256), 0,
+                           RNG_STREAM, pk.sel_coset, pk.sig_coset, cs->coset_out,
+                           pk.l1_coset, mp->xpow, cs->q_all, m, k, cs->chs);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(RNG_STREAM));  // chs_h lifetime
+    }
+    // batched inverse coset NTT of the k quotients
+    rc = ntt_dev_run(ctx, cs->q_all, cs->ntt_tmp, m, k, true, RNG_STREAM);
+    if (rc != RNG_OK) return rc;
+    uint64_t total_q = (uint64_t)k * m;
+    hipLaunchKernelGGL(k_mul_pointwise_mod, dim3((uint32_t)((total_q + 255) / 256)),
+                       dim3(256), 0, RNG_STREAM, cs->ntt_tmp, mp->gpow_inv, m,
+                       total_q);
+    HIP_CHECK(hipGetLastError());
+    // chunk-split + linking blinders ON DEVICE, into the commit's staging
+    HIP_CHECK(hipMemcpyAsync(cs->blinders, qblind_h, 4 * (size_t)k * sizeof(Fr),
+                             hipMemcpyHostToDevice, RNG_STREAM));
+    uint64_t total_c = 5 * (uint64_t)k * (n + 3);
+    hipLaunchKernelGGL(k_quot_chunks_batch,
+                       dim3((uint32_t)((total_c + 255) / 256)), dim3(256), 0,
+                       RNG_STREAM, cs->ntt_tmp, cs->blinders, cs->stage,
+                       (uint32_t)n, m, total_c);
+    HIP_CHECK(hipGetLastError());
+    return RNG_OK;
+}
+
 // k >= 1 proofs in lockstep under ONE proving key (the headline shape: a
 // stream of same-circuit jobs); the only prover, behind rng_prove (k = 1) and
 // rng_prove_cohort.  One ProofState per proof runs the shared host rounds of
@@ -2347,71 +2422,14 @@ static int plonk_prove_impl(RngCtxImpl* ctx, const PlonkPkImpl& pk, uint32_t k,
     COHORT_TRACE("r3");
     // --- R3: coset transforms (batched) + quotient + fused MSM ---
     {
-        NttPlan* mp = get_plan(ctx, m, 0);  // tables only; batch NTTs below
-        if (!mp || ensure_coset_tables(ctx, mp) != RNG_OK) return RNG_ERR_HIP;
-        const uint64_t stride = n + 3;
-        uint64_t total_in = 7 * (uint64_t)k * stride;
-        uint64_t total_m = 7 * (uint64_t)k * m;
-        if (open_on) {
-            // R4 + R5 read the plain coefficients again: scale while padding,
-            // out of place
-            hipLaunchKernelGGL(k_scale_pad_batch, dim3((uint32_t)((total_m + 255) / 256)),
-                               dim3(256), 0, RNG_STREAM, (const Fr*)cs->coset_in,
-                               (uint32_t)stride, (const Fr*)mp->gpow, cs->ntt_tmp, m,
-                               total_m);
-            HIP_CHECK(hipGetLastError());
-        } else {
-            hipLaunchKernelGGL(k_mul_pointwise_mod,
-                               dim3((uint32_t)((total_in + 255) / 256)), dim3(256), 0,
-                               RNG_STREAM, cs->coset_in, mp->gpow, (uint32_t)stride,
-                               total_in);
-            HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_copy_pad_batch, dim3((uint32_t)((total_m + 255) / 256)),
-                               dim3(256), 0, RNG_STREAM, cs->coset_in, (uint32_t)stride,
-                               cs->ntt_tmp, m, total_m);
-            HIP_CHECK(hipGetLastError());
-        }
-        int rc = ntt_dev_run(ctx, cs->ntt_tmp, cs->coset_out, m, 7 * (uint64_t)k, false,
-                             RNG_STREAM);
-        if (rc != RNG_OK) return rc;
-
-        // ONE batched quotient launch for all k proofs (a single proof's m
-        // grid is latency-starved; 483 small launches were 14% of cohort GPU
-        // time in the r02 profile)
-        {
-            std::vector<QuotChal> chs_h(k, quot_chal_fixed(pk));
-            for (uint32_t p = 0; p < k; ++p) quot_chal_set(chs_h[p], st[p]);
-            HIP_CHECK(hipMemcpyAsync(cs->chs, chs_h.data(), k * sizeof(QuotChal),
-                                     hipMemcpyHostToDevice, RNG_STREAM));
-            uint64_t total_kq = (uint64_t)k * m;
-            hipLaunchKernelGGL(k_quotient_batch,
-                               dim3((uint32_t)((total_kq + 255) / 256)), dim3(256), 0,
-                               RNG_STREAM, pk.sel_coset, pk.sig_coset, cs->coset_out,
-                               pk.l1_coset, mp->xpow, cs->q_all, m, k, cs->chs);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(RNG_STREAM));  // chs_h lifetime
-        }
-        // batched inverse coset NTT of the k quotients
-        rc = ntt_dev_run(ctx, cs->q_all, cs->ntt_tmp, m, k, true, RNG_STREAM);
-        if (rc != RNG_OK) return rc;
-        uint64_t total_q = (uint64_t)k * m;
-        hipLaunchKernelGGL(k_mul_pointwise_mod, dim3((uint32_t)((total_q + 255) / 256)),
-                           dim3(256), 0, RNG_STREAM, cs->ntt_tmp, mp->gpow_inv, m,
-                           total_q);
-        HIP_CHECK(hipGetLastError());
-        // chunk-split + linking blinders ON DEVICE, commit from the staged
-        // buffer; the blinded chunks stream back D2H for the host R5
-        // linearization (complete after the commit's internal sync)
+        std::vector<QuotChal> chs_h(k, quot_chal_fixed(pk));
+        for (uint32_t p = 0; p < k; ++p) quot_chal_set(chs_h[p], st[p]);
         std::vector<Fr> qblind_h = pack_blinders(BLIND_CHUNKS, 4);
-        HIP_CHECK(hipMemcpyAsync(cs->blinders, qblind_h.data(),
-                                 qblind_h.size() * sizeof(Fr),
-                                 hipMemcpyHostToDevice, RNG_STREAM));
+        int rc = quotient_stage(ctx, pk, k, cs, open_on, chs_h.data(), qblind_h.data());
+        if (rc != RNG_OK) return rc;
+        // the blinded chunks stream back D2H for the host R5 linearization
+        // (complete after the commit's internal sync)
         uint64_t total_c = 5 * (uint64_t)k * (n + 3);
-        hipLaunchKernelGGL(k_quot_chunks_batch,
-                           dim3((uint32_t)((total_c + 255) / 256)), dim3(256), 0,
-                           RNG_STREAM, cs->ntt_tmp, cs->blinders, cs->stage,
-                           (uint32_t)n, m, total_c);
-        HIP_CHECK(hipGetLastError());
         std::vector<Fr> chunks_host(open_on ? 0 : total_c);
         if (!open_on)
             HIP_CHECK(hipMemcpyAsync(chunks_host.data(), cs->stage,
@@ -3299,6 +3317,45 @@ int rng_open_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t
         memcpy(o, Wz.data(), (n + 2) * sizeof(Fr));
         memcpy(o + (n + 2), Wzw.data(), (n + 2) * sizeof(Fr));
     });
+    return RNG_OK;
+}
+
+int rng_quotient_pk(RngCtx* ctx, const RngProvingKey* pk, uint64_t k, const uint64_t* polys,
+                    const uint64_t* challenges, const uint64_t* blinders, int mode,
+                    uint64_t* out_chunks, uint64_t* out_quot) {
+    if (!gpu_ok()) return RNG_ERR_NO_GPU;
+    if (!ctx || !pk || !polys || !challenges || !out_chunks || k < 1 ||
+        k > OPEN_MAX_BATCH || mode < 0 || mode > 2)
+        return RNG_ERR_BAD_ARG;
+    const PlonkPkImpl& impl = pk->impl;
+    const uint64_t n = impl.n, m = 8 * n;
+    bool oop = mode == 1;
+    if (mode == 0)
+        oop = ProverEnv::on(prover_env().open_device, OPEN_DEVICE_DEFAULT) && n <= OPEN_MAX_N;
+    if (cohort_scratch_ensure(n, k) != RNG_OK) return RNG_ERR_HIP;
+    CohortScratch* cs = tls_cohort_scratch.get();
+    std::vector<QuotChal> chs_h(k, quot_chal_fixed(impl));
+    const Fr* ch = (const Fr*)challenges;
+    for (uint64_t p = 0; p < k; ++p) {
+        chs_h[p].beta = ch[3 * p];
+        chs_h[p].gamma = ch[3 * p + 1];
+        chs_h[p].alpha = ch[3 * p + 2];
+        chs_h[p].alpha2 = ch[3 * p + 2].sqr();
+    }
+    std::vector<Fr> qblind_h(4 * k, Fr::zero());
+    if (blinders) memcpy(qblind_h.data(), blinders, 4 * k * sizeof(Fr));
+    const size_t chunk_elems = 5 * k * (n + 3);
+    HIP_CHECK(hipMemcpyAsync(cs->coset_in, polys, 7 * k * (n + 3) * sizeof(Fr),
+                             hipMemcpyHostToDevice, RNG_STREAM));
+    int rc = quotient_stage(&ctx->impl, impl, (uint32_t)k, cs, oop, chs_h.data(),
+                            qblind_h.data());
+    if (rc != RNG_OK) return rc;
+    HIP_CHECK(hipMemcpyAsync(out_chunks, cs->stage, chunk_elems * sizeof(Fr),
+                             hipMemcpyDeviceToHost, RNG_STREAM));
+    if (out_quot)
+        HIP_CHECK(hipMemcpyAsync(out_quot, cs->ntt_tmp, k * m * sizeof(Fr),
+                                 hipMemcpyDeviceToHost, RNG_STREAM));
+    HIP_CHECK(hipStreamSynchronize(RNG_STREAM));  // qblind_h lifetime, outputs complete
     return RNG_OK;
 }
 

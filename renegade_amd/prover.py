@@ -81,6 +81,9 @@ class ProverLib:
                                              _U64P, ctypes.c_int, _U64P]
         self.lib.rng_open_pk.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                          _U64P, _U64P, _U64P, ctypes.c_int, _U64P]
+        self.lib.rng_quotient_pk.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint64, _U64P, _U64P, _U64P,
+                                             ctypes.c_int, _U64P, _U64P]
         self.lib.rng_srs_dev_bases.restype = ctypes.c_void_p
         self.lib.rng_srs_dev_bases.argtypes = [ctypes.c_void_p, _U64P]
 
@@ -264,6 +267,33 @@ class ProverCtx:
         self._check(self.lib.rng_open_pk(self.h, ctypes.c_void_p(pk), k, *map(_ptr, args),
                                          mode, _ptr(out)), "rng_open_pk")
         return out.reshape(k, 2, n + 2, 4)
+
+    QUOT_AUTO, QUOT_OUT_OF_PLACE, QUOT_IN_PLACE = 0, 1, 2
+
+    def quotient_pk(self, pk, polys: np.ndarray, challenges: np.ndarray, n: int,
+                    k: int = 1, blinders=None, mode: int = 0):
+        """The prover's own round-3 call against proving key `pk` (domain
+        size n): polys k*7*(n+3) Fr (wires 0..4, z, PI, zero-padded),
+        challenges k*(beta, gamma, alpha), blinders k*4 chunk blinders or
+        None for zeros.  mode: QUOT_AUTO / QUOT_OUT_OF_PLACE / QUOT_IN_PLACE
+        (the two coset-extension arms).  Returns (chunks, quot): the blinded
+        chunks, (k, 5, n + 3, 4), and every quotient coefficient before the
+        split, (k, 8n, 4)."""
+        for a, fr in ((polys, 7 * (n + 3) * k), (challenges, 3 * k)):
+            assert a.dtype == np.uint64 and a.size == 4 * fr
+        polys = np.ascontiguousarray(polys).reshape(-1)
+        challenges = np.ascontiguousarray(challenges).reshape(-1)
+        bptr = None
+        if blinders is not None:
+            assert blinders.dtype == np.uint64 and blinders.size == 4 * 4 * k
+            blinders = np.ascontiguousarray(blinders).reshape(-1)
+            bptr = _ptr(blinders)
+        chunks = np.zeros(4 * 5 * (n + 3) * k, dtype=np.uint64)
+        quot = np.zeros(4 * 8 * n * k, dtype=np.uint64)
+        self._check(self.lib.rng_quotient_pk(self.h, ctypes.c_void_p(pk), k, _ptr(polys),
+                                             _ptr(challenges), bptr, mode, _ptr(chunks),
+                                             _ptr(quot)), "rng_quotient_pk")
+        return chunks.reshape(k, 5, n + 3, 4), quot.reshape(k, 8 * n, 4)
 
     # ---- device-resident helpers (benchmarking) ----
     def dbuf_from(self, host: np.ndarray):
